@@ -2,7 +2,7 @@
 """Benchmark of the MI355X WORLD hot path (BASELINE.json metric: analysis+synthesis frames/s and xRT,
 16 kHz / 5 ms hop).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -21,7 +21,13 @@ un-captured pass of the same K steps right after it (events cannot be read back 
 (per-rank input generation, sharding, barrier, max / sum reductions, `per_rank_ms`) runs end to end on a one-GPU lease;
 the line says `"shared_gpu": true` and is NOT a scaling measurement.
 
-Rank 0 prints ONE JSON line.  On a single GPU it also carries (each timed by this process):
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: inputs, upload, warm-up, capture,
+the K timed steps, the device condition flags they raised, and with `--dump-outputs DIR` what the last timed step returned
+to its caller (DIR/<name>.npy: f0, vuv, temporal_positions, spectrogram, aperiodicity, out, out_offsets; an array above 4
+MiB as a seeded sample of its rows with <name>_index.npy beside it; inputs are seeded, so equal arguments give equal
+inputs).  Everything else runs with `--full`: the one-in-flight re-run (`ms_per_step_one_in_flight`), the profiled
+un-captured pass (`eager_ms_per_step`, `kernel_ms`, `roofline`, with the PMC child runs) and, on a single GPU, the
+blocks below (each timed by this process):
   cpu_baseline   : the NumPy oracle on the host cores (1 core and all cores, median of 3), bounded sample;
   with_transfers : config 2 once more with the H2D of x and the D2H of f0/vuv/spectrogram/aperiodicity/out through
                    pinned buffers inside the timed region (what a host-buffer caller sees; never `value`);
@@ -53,6 +59,10 @@ SECONDS = 10.0
 UTT_PER_GPU = 64
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 FP64_VECTOR_PEAK_TFLOPS = 78.6  # FP64 vector FMA: 256 CUs x 4 SIMDs x 16 lanes/clk x 2 flop x 2.4 GHz (the SIMD-16 ceiling)
+# --dump-outputs: at most this much per array (and as much again for a sample's row indices): six sampled arrays
+# (config 4 at 1024 utterances) stay under 64 MB in all
+DUMP_ARRAY_BYTES = 4 << 20
+DUMP_TOTAL_BYTES = 64 * 10 ** 6
 
 
 # Algorithmic (compulsory) HBM bytes per 5 ms frame of each dominant-kernel candidate, float64 API dtypes —
@@ -113,7 +123,18 @@ def parse():
                     help="BASELINE.json config: 2 = DIO path encode+decode (the metric's config, default); "
                          "3 = Harvest F0 only; 4 = Harvest + CheapTrick + D4C-Requiem encode + Requiem decode; "
                          "5 = 48 kHz long-form: Harvest encode, scale_pitch(1.5), scale_duration(2.0), decode")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: CPU baselines, the one-in-flight re-run, per-kernel times and "
+                         "roofline, PMC child runs, the extra blocks (--no-cpu-baseline / --no-extras / --no-pmc still opt "
+                         "out of parts).  Without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller as DIR/<name>.npy "
+                         "(rank 0's share; arrays above %d MiB as a fixed, seeded sample of their rows)" % (DUMP_ARRAY_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_extras = args.no_pmc = True
     if args.utts is None:
         args.utts = 16 if args.config == 5 else UTT_PER_GPU
     if args.seconds is None:
@@ -341,7 +362,7 @@ def measure_pmc_traffic(args, timeout_s=240, config=None, utts=None, seconds=Non
     tmp = tempfile.mkdtemp(prefix="wh_pmc_", dir=os.environ.get("TMPDIR", "/tmp"))
     child = [sys.executable, os.path.abspath(__file__), "--config", str(config or args.config),
              "--utts", str(utts or args.utts), "--seconds", str(seconds or args.seconds), "--steps", str(steps),
-             "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--no-graph", "--no-pmc", "--in-flight", "1"]
+             "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras", "--no-graph", "--no-pmc", "--in-flight", "1"]
     per = {}
     try:
         LAST_SQ.clear()
@@ -526,7 +547,9 @@ def main():
     fence()
 
     def run_steps(active):
-        """K steps dealt round-robin to the first `active` pipelines; returns (host enqueue time, wall time)."""
+        """K steps dealt round-robin to the first `active` pipelines; returns (host enqueue time, wall time, what the
+        last step returned)."""
+        last = None
         t0 = time.perf_counter()
         for k in range(args.steps):
             d = k % active
@@ -536,31 +559,44 @@ def main():
                         graphs[d].replay()
                 else:
                     graphs[d].replay()
+                if k == args.steps - 1:
+                    last = graphs[d]._keep  # a replay rewrites the outputs the capture returned, in place
             else:
-                steps_fn[d](1000 + k)
+                res = steps_fn[d](1000 + k)
+                if k == args.steps - 1:
+                    last = res
+                del res  # (an eager step's outputs go back to the allocator before the next step, as they always did)
         enq = time.perf_counter() - t0  # the launches are asynchronous: host time to enqueue all K steps
         fence()
-        return enq, time.perf_counter() - t0
+        return enq, time.perf_counter() - t0, last
 
-    host_enqueue, elapsed = run_steps(depth)
-    one_in_flight = None
-    if depth > 1:  # the same K steps with one step in flight at a time (pipeline 0 alone), for the record
+    host_enqueue, elapsed, last = run_steps(depth)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step_outputs(args.config, last), args.dump_outputs)
+    del last
+    flags = [0] * 16
+    for w_ in wls:  # conditions the kernels of the timed steps raised, every pipeline
+        for wb in w_.lanes:
+            flags = [a | b for a, b in zip(flags, wb.rt.take_flags())]
+    one_in_flight = eager_elapsed = None
+    records = []
+    if args.full:
+        if depth > 1:  # the same K steps with one step in flight at a time (pipeline 0 alone), for the record
+            fence()
+            _, one_in_flight, _ = run_steps(1)
+
+        # ---- un-captured pass of the same K steps with a HIP-event pair around every kernel launch --------------
+        for rt in rts:
+            rt.profile(True)
+        tp0 = time.perf_counter()
+        for k in range(args.steps):
+            step(1000 + k)
         fence()
-        _, one_in_flight = run_steps(1)
-
-    # ---- un-captured pass of the same K steps with a HIP-event pair around every kernel launch ------------------
-    for rt in rts:
-        rt.profile(True)
-    tp0 = time.perf_counter()
-    for k in range(args.steps):
-        step(1000 + k)
-    fence()
-    eager_elapsed = time.perf_counter() - tp0
-    records, flags = [], [0] * 16
-    for rt in rts:
-        records += rt.profile_collect()
-        rt.profile(False)
-        flags = [a | b for a, b in zip(flags, rt.take_flags())]
+        eager_elapsed = time.perf_counter() - tp0
+        for rt in rts:
+            records += rt.profile_collect()
+            rt.profile(False)
+            flags = [a | b for a, b in zip(flags, rt.take_flags())]
 
     per_rank_ms = [elapsed / args.steps * 1e3]
     if dist.is_initialized():
@@ -660,9 +696,9 @@ def main():
             "ms_per_step": elapsed / args.steps * 1e3,
             "steps_in_flight": depth,
             "headline_definition": "ms_per_step / value: %d whole step(s) in flight (the default since round 5; rounds 1-4 "
-                                   "timed one: that figure is ms_per_step_one_in_flight in every line)" % depth,
+                                   "timed one: that figure is ms_per_step_one_in_flight in every --full line)" % depth,
             "primed": args.warmup == 0,
-            "ms_per_step_one_in_flight": None if one_in_flight is None else one_in_flight / args.steps * 1e3,
+            "full": args.full,
             "per_rank_ms": [round(v, 4) for v in per_rank_ms],
             "higher_is_better": True,
             "scaling": args.scaling,
@@ -671,16 +707,20 @@ def main():
             "data": "synthetic",
             "x_realtime": audio_s / elapsed,
             "graph": graph is not None,
-            "eager_ms_per_step": eager_elapsed / args.steps * 1e3,
             "host_enqueue_ms_per_step": host_enqueue / args.steps * 1e3,
             "config": {"workload": workloads[args.config] % (count, args.seconds),
                        "utterances_per_gpu": count, "distinct_utterances": distinct, "fs": FS, "frame_period_ms": 5,
                        "frames_per_step_per_gpu": frames_per_step, "sharding": "utterances, no collective",
                        "lanes_per_gpu": len(rts)},
-            "roofline": roofline,
-            "kernel_ms": {k: round(v, 4) for k, v in sorted(kernel_ms.items(), key=lambda kv: -kv[1])},
             "device_flags": flags,
         }
+        if args.full:
+            out.update({
+                "ms_per_step_one_in_flight": None if one_in_flight is None else one_in_flight / args.steps * 1e3,
+                "eager_ms_per_step": eager_elapsed / args.steps * 1e3,
+                "roofline": roofline,
+                "kernel_ms": {k: round(v, 4) for k, v in sorted(kernel_ms.items(), key=lambda kv: -kv[1])},
+            })
         if share_gpu:
             out["shared_gpu"] = True
             out["config"]["parallelism"] = "%d ranks time-sharing ONE GPU over gloo (WH_BENCH_SHARE_GPU=1): a rehearsal " \
@@ -739,10 +779,12 @@ def main():
 
 
 def make_step(args, wl, fs):
+    """One step over the resident batch; returns what its caller receives (step_outputs reads it): (encodings, decodes)
+    per lane, or per lane Harvest's (f0, vuv) for config 3."""
     if args.config == 2:
         def step(seed):
             encs = wl.encode_device(fs, stagger=not args.no_stagger, f0_method="dio")
-            return wl.decode_device(encs, seed=seed)
+            return encs, wl.decode_device(encs, seed=seed)
     elif args.config == 3:
         from world.harvest import harvest_device
 
@@ -758,12 +800,66 @@ def make_step(args, wl, fs):
             for e in encs:
                 with e.rt.on_stream():
                     e.scale_pitch(1.5).scale_duration(2.0)
-            return wl.decode_device(encs, seed=seed)
+            return encs, wl.decode_device(encs, seed=seed)
     else:
         def step(seed):
             encs = wl.encode_device(fs, stagger=not args.no_stagger, f0_method="harvest", is_requiem=True)
-            return wl.decode_device(encs)  # seed tables: generated on the device once (wh_requiem_seeds), resident
+            return encs, wl.decode_device(encs)  # seed tables: generated on the device once (wh_requiem_seeds), resident
     return step
+
+
+def step_outputs(config, result):
+    """[(name, device tensor)] of one step's result (make_step), the lanes' parts joined in utterance order: per frame
+    temporal_positions, f0, vuv, the frame-major spectrogram and aperiodicity, the concatenated waveforms `out` and
+    `out_offsets` (utterance u is out[out_offsets[u]:out_offsets[u + 1]]); config 3: f0 and vuv."""
+    import torch
+
+    if config == 3:
+        parts = [r for r in result if r is not None]
+        return [("f0", torch.cat([p[0] for p in parts])), ("vuv", torch.cat([p[1] for p in parts]))]
+    encs, decs = result
+    parts = [(e, d) for e, d in zip(encs, decs) if e is not None]
+    named = [(k, torch.cat([getattr(e, k) for e, _ in parts]))
+             for k in ("temporal_positions", "f0", "vuv", "spectrogram", "aperiodicity")]
+    offsets, base = [0], 0
+    for _, (y, y_off) in parts:
+        offsets += [base + int(v) for v in y_off[1:]]
+        base += int(y.shape[0])
+    named.append(("out", torch.cat([y for _, (y, _) in parts])))
+    named.append(("out_offsets", torch.tensor(offsets, dtype=torch.float64)))
+    return named
+
+
+def dump_outputs(named, out_dir):
+    """Write every (name, tensor) of ``named`` as out_dir/<name>.npy: float32 stays float32, anything else is float64.  An
+    array above DUMP_ARRAY_BYTES is written as a fixed sample of its rows (first axis): one row drawn from each of k equal
+    strata by a RandomState seeded with the name, in order, their indices in out_dir/<name>_index.npy."""
+    import zlib
+
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in named:
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        n = int(t.shape[0])
+        row_bytes = t.element_size() * (t.numel() // max(n, 1))
+        if n and t.numel() * t.element_size() > DUMP_ARRAY_BYTES:
+            k = max(1, min(n, DUMP_ARRAY_BYTES // row_bytes))
+            lo = np.arange(k, dtype=np.int64) * n // k
+            hi = np.arange(1, k + 1, dtype=np.int64) * n // k
+            u = np.random.RandomState(zlib.crc32(name.encode())).random_sample(k)
+            rows = lo + (u * (hi - lo)).astype(np.int64)
+            index = rows.astype(np.float64)
+            np.save(os.path.join(out_dir, name + "_index.npy"), index)
+            total += index.nbytes
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    if total > DUMP_TOTAL_BYTES:
+        raise RuntimeError("--dump-outputs wrote %d bytes, more than %d" % (total, DUMP_TOTAL_BYTES))
 
 
 def try_capture(torch, fn, stream=None):

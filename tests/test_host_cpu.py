@@ -421,6 +421,57 @@ def test_bench_defaults_match_the_contract(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--config", "5", "--in-flight", "1"])
     b = bench.parse()
     assert (b.utts, b.seconds, b.in_flight) == (16, 60.0, 1)
+    # a plain run times the headline only; --full is everything else, its opt-outs unchanged
+    assert not a.full and a.no_cpu_baseline and a.no_extras and a.no_pmc and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-pmc", "--steps", "7", "--dump-outputs", "d"])
+    c = bench.parse()
+    assert c.full and c.no_pmc and not c.no_cpu_baseline and not c.no_extras and (c.steps, c.dump_outputs) == (7, "d")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_bench_dump_outputs_joins_lanes_and_samples_large_arrays(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the lanes' parts of a step's result in utterance order, out_offsets into the joined audio,
+    arrays above the per-array budget as seeded stratified row samples (the same rows every run, with their indices),
+    everything float32 / float64."""
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_ARRAY_BYTES", 4096)
+
+    def lane(nf, ny, u):
+        g = torch.Generator().manual_seed(u)
+        e = types.SimpleNamespace(temporal_positions=torch.arange(nf, dtype=torch.float64) * 0.005,
+                                  f0=torch.rand(nf, generator=g, dtype=torch.float64),
+                                  vuv=(torch.rand(nf, generator=g) > 0.5).to(torch.int32),
+                                  spectrogram=torch.rand(nf, 33, generator=g, dtype=torch.float64),
+                                  aperiodicity=torch.rand(nf, 5, generator=g, dtype=torch.float32))
+        return e, (torch.rand(ny, generator=g, dtype=torch.float64), np.array([0, ny // 3, ny], dtype=np.int64))
+
+    (e0, d0), (e1, d1) = lane(300, 2000, 1), lane(200, 1500, 2)
+    named = dict(bench.step_outputs(2, ([e0, None, e1], [d0, None, d1])))
+    assert named["out_offsets"].tolist() == [0, 666, 2000, 2500, 3500]
+    assert torch.equal(named["vuv"], torch.cat([e0.vuv, e1.vuv]))
+    runs = []
+    for r in range(2):
+        bench.dump_outputs(list(named.items()), str(tmp_path / str(r)))
+        runs.append({p.name: np.load(p) for p in (tmp_path / str(r)).iterdir()})
+    assert runs[0].keys() == runs[1].keys() and all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
+    got = runs[0]
+    assert {k: v.dtype for k, v in got.items() if not k.endswith("_index.npy")} == {
+        "temporal_positions.npy": np.float64, "f0.npy": np.float64, "vuv.npy": np.float64, "spectrogram.npy": np.float64,
+        "aperiodicity.npy": np.float32, "out.npy": np.float64, "out_offsets.npy": np.float64}
+    assert np.array_equal(got["f0.npy"], named["f0"].numpy()) and "f0_index.npy" not in got       # 4000 B: whole
+    for k in ("spectrogram", "out"):
+        idx = got[k + "_index.npy"].astype(np.int64)
+        assert got[k + ".npy"].nbytes <= 4096 and len(idx) >= 2 and np.all(np.diff(idx) > 0)
+        assert np.array_equal(got[k + ".npy"], named[k].numpy()[idx])
+    assert [k for k, _ in bench.step_outputs(3, [(e0.f0, e0.vuv), (e1.f0, e1.vuv)])] == ["f0", "vuv"]
 
 
 

@@ -8,7 +8,7 @@ shift
 mkdir -p $O
 for v in "$@"; do
   if [ "$v" = "base" ]; then unset WH_LIB; else export WH_LIB=$PWD/python-world_amd/lib/variants/libworld_hip_$v.so; fi
-  python bench.py "${FL[@]}" --no-extras --no-cpu-baseline > $O/b_$v.json 2> $O/b_$v.err
+  python bench.py --full "${FL[@]}" --no-extras --no-cpu-baseline > $O/b_$v.json 2> $O/b_$v.err
   python - "$O/b_$v.json" "$v" <<'PY'
 import json, sys
 try:

@@ -10,15 +10,15 @@ export TMPDIR=/tmp
 O=gpurun_out/$1; mkdir -p $O
 ( time timeout 1500 python -m pytest tests -m gpu -q --durations=5 ) > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log; tail -3 $O/pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-( time python bench.py ) > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
-python bench.py --config 3 --steps 10 --warmup 2 --no-pmc > $O/bench_cfg3.json 2> $O/bench_cfg3.err
-python bench.py --config 3 --utts 256 --steps 6 --warmup 1 --no-pmc > $O/bench_cfg3_256.json 2> $O/bench_cfg3_256.err
-python bench.py --config 4 --steps 10 --warmup 2 --no-pmc > $O/bench_cfg4.json 2> $O/bench_cfg4.err
-python bench.py --config 5 --steps 4 --warmup 1 --no-pmc > $O/bench_cfg5.json 2> $O/bench_cfg5.err
+( time python bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+python bench.py --full --config 3 --steps 10 --warmup 2 --no-pmc > $O/bench_cfg3.json 2> $O/bench_cfg3.err
+python bench.py --full --config 3 --utts 256 --steps 6 --warmup 1 --no-pmc > $O/bench_cfg3_256.json 2> $O/bench_cfg3_256.err
+python bench.py --full --config 4 --steps 10 --warmup 2 --no-pmc > $O/bench_cfg4.json 2> $O/bench_cfg4.err
+python bench.py --full --config 5 --steps 4 --warmup 1 --no-pmc > $O/bench_cfg5.json 2> $O/bench_cfg5.err
 TR="python -m torch.distributed.run --nnodes=1 --master-addr 127.0.0.1"
-$TR --nproc-per-node 1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 3 --no-extras --no-cpu-baseline --no-pmc > $O/rehearsal_torchrun_n1.log 2>&1
-WH_BENCH_SHARE_GPU=1 $TR --nproc-per-node 2 --master-port 29518 bench.py --gpus 2 --steps 10 --warmup 2 --no-extras --no-cpu-baseline --no-pmc > $O/rehearsal_share_gpu_n2_weak.log 2>&1
-WH_BENCH_SHARE_GPU=1 $TR --nproc-per-node 2 --master-port 29519 bench.py --gpus 2 --config 4 --utts 128 --scaling strong --steps 6 --warmup 2 --no-extras --no-cpu-baseline --no-pmc > $O/rehearsal_share_gpu_n2_strong_cfg4.log 2>&1
+$TR --nproc-per-node 1 --master-port 29517 bench.py --full --gpus 1 --steps 20 --warmup 3 --no-extras --no-cpu-baseline --no-pmc > $O/rehearsal_torchrun_n1.log 2>&1
+WH_BENCH_SHARE_GPU=1 $TR --nproc-per-node 2 --master-port 29518 bench.py --full --gpus 2 --steps 10 --warmup 2 --no-extras --no-cpu-baseline --no-pmc > $O/rehearsal_share_gpu_n2_weak.log 2>&1
+WH_BENCH_SHARE_GPU=1 $TR --nproc-per-node 2 --master-port 29519 bench.py --full --gpus 2 --config 4 --utts 128 --scaling strong --steps 6 --warmup 2 --no-extras --no-cpu-baseline --no-pmc > $O/rehearsal_share_gpu_n2_strong_cfg4.log 2>&1
 python - "$O" <<'PY'
 import json, sys, glob
 for f in sorted(glob.glob(sys.argv[1] + "/bench_*.json")) + sorted(glob.glob(sys.argv[1] + "/rehearsal_*.log")):

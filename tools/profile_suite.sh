@@ -9,7 +9,7 @@ CFG=$1; TAG=$2; shift 2
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="python bench.py --config $CFG --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-graph $*"
+B="python bench.py --full --config $CFG --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-graph $*"
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t --output-format csv -- $B > $OUT/trace.json 2> $OUT/trace.err
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/fetch -o f --output-format csv -- $B > /dev/null 2> $OUT/fetch.err
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/write -o w --output-format csv -- $B > /dev/null 2> $OUT/write.err

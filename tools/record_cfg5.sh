@@ -1,7 +1,7 @@
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 O=gpurun_out/r06s3_cfg5; mkdir -p $O/digests
-python bench.py --config 5 --steps 4 --warmup 1 --no-pmc > $O/bench_cfg5.json 2> $O/bench_cfg5.err
+python bench.py --full --config 5 --steps 4 --warmup 1 --no-pmc > $O/bench_cfg5.json 2> $O/bench_cfg5.err
 timeout 900 tools/profile_suite.sh 5 r06s3_cfg5/prof_cfg5 --in-flight 1 > $O/prof5.log 2>&1; echo "profile cfg5 rc=$?"
 d=$O/prof_cfg5
 cp $d/trace/t_kernel_stats.csv $O/digests/cfg5_kernel_stats.csv
