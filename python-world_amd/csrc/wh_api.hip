@@ -167,7 +167,7 @@ int wh_ctx_create(int device, wh_ctx** out) {
   wh_ctx* c = new wh_ctx();
   c->device = device;
   // twiddle tables: for N = 2,4,..,WH_MAX_TWIDDLE the table exp(-2*pi*i*k/N), k<N, lives at [N, 2N)
-  std::vector<double2> tw(2 * WH_MAX_TWIDDLE);
+  std::vector<double2> tw(WH_TWIDDLE_ENTRIES);
   tw[0] = tw[1] = make_double2(1.0, 0.0);
   for (int n = 2; n <= WH_MAX_TWIDDLE; n <<= 1) {
     for (int k = 0; k < n; ++k) {
@@ -182,6 +182,11 @@ int wh_ctx_create(int device, wh_ctx** out) {
       tw[n + 3 * n / 4] = make_double2(0.0, 1.0);
     }
   }
+  // behind them the FFT passes' [k][r] tables (wh_device.h, fft_ptw_offset): copies of the size-M tables' entries k r
+  for (int R = 2; R <= 8; R <<= 1)
+    for (int m = R; m <= WH_MAX_FFT; m <<= 1)
+      for (int k = 0; k < m / R; ++k)
+        for (int r = 1; r < R; ++r) tw[wh::fft_ptw_offset(m, R) + k * (R - 1) + r - 1] = tw[m + k * r];
   hipError_t e = hipMalloc((void**)&c->d_twiddle, tw.size() * sizeof(double2));
   if (e == hipSuccess) e = hipMemcpy(c->d_twiddle, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc((void**)&c->d_flags, 16 * sizeof(int32_t));

@@ -23,6 +23,13 @@
 #define WH_TID threadIdx.x
 #endif
 
+#define WH_MAX_FFT 8192  // longest in-LDS transform (CheapTrick / synthesis stop at 4096, D4C / love-train / SWIPE' at 8192)
+// The twiddle tables go further: StoneMask and the Harvest refinement evaluate a handful of bins of a transform of
+// 2^(2 + floor(log2(window))) points directly (stonemask.py:33-35) — no transform is run, only exp(-2 pi i k / n) is
+// looked up — and a 3-period window at a low floor and a high rate asks for 16384 or 32768 (96 kHz below 70 Hz, 48 kHz
+// below 35 Hz: the fft_size override).  1 MB per context.
+#define WH_MAX_TWIDDLE 32768
+
 namespace wh {
 
 // Loads that are known to address global memory, said so to the compiler.  Kernel-argument pointers are inferred as
@@ -417,6 +424,19 @@ __device__ __forceinline__ double2 cmul_conj(double2 a, double2 b) {
 #endif
 __device__ __forceinline__ int fft_swz(int i) { return i ^ ((i >> 3) & 7); }
 
+// Pass twiddles.  The context's table of size n lives at [n, 2n) of d_twiddle (wh_api.hip); behind those tables (0.56 MB),
+// from 2 * WH_MAX_TWIDDLE on, every radix R in {2, 4, 8} has one table per pass span M = NS * R <= WH_MAX_FFT, laid out
+// [k][r]: entry k * (R - 1) + r - 1 = exp(-2 pi i k r / M), k < M / R, 1 <= r < R.  A butterfly's R - 1 twiddles are then
+// R - 1 consecutive entries: one address per butterfly and immediate offsets, where the size-N table needed R - 1
+// products (k r N / M) & (N - 1).  The entries are copies of the size-M table's entry k r, which is the size-N table's
+// entry k r N / M bit for bit (the host computes exp(-2 pi i k / n) as -2 pi k / n in long double: scaling k and n by
+// the same power of two scales the rounded angle exactly), so the transforms' results do not change.
+constexpr int fft_ptw_count(int R) { return (2 * WH_MAX_FFT / R - 1) * (R - 1); }  // entries of radix R's tables
+constexpr int fft_ptw_offset(int M, int R) {                                       // table (M, R), from d_twiddle
+  return 2 * WH_MAX_TWIDDLE + (R >= 4 ? fft_ptw_count(2) : 0) + (R >= 8 ? fft_ptw_count(4) : 0) + (M / R - 1) * (R - 1);
+}
+#define WH_TWIDDLE_ENTRIES (2 * WH_MAX_TWIDDLE + wh::fft_ptw_count(2) + wh::fft_ptw_count(4) + wh::fft_ptw_count(8))
+
 __device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
 // multiply by -i (forward) / +i (inverse)
@@ -513,7 +533,8 @@ __device__ __forceinline__ void fft_pass_twiddles(ckp<const double2> WH_RESTRICT
   constexpr int PER = (J + NT - 1) / NT;
   const int tid = WH_TID & (NT - 1);
   if (NS > 1) {
-    constexpr int STEP = N / (NS * R);
+    static_assert(NS * R <= WH_MAX_FFT, "pass twiddle tables stop at WH_MAX_FFT");
+    const ckp<const double2> pt = tw + (fft_ptw_offset(NS * R, R) - N);  // tw: the size-N table, at offset N
 #pragma unroll
     for (int p = 0; p < PER; ++p) {
       const int j = tid + p * NT;
@@ -523,7 +544,7 @@ __device__ __forceinline__ void fft_pass_twiddles(ckp<const double2> WH_RESTRICT
         for (int r = 1; r < R; ++r) {
           // as stored: the inverse transform's conjugation is folded into the multiply (fft_pass_finish) — negating
           // here made every load's wait come right behind it, in front of the pass's LDS reads instead of under them
-          w[p][r] = ldg2(tw + ((k * r * STEP) & (N - 1)));
+          w[p][r] = ldg2(pt + (k * (R - 1) + r - 1));
         }
       }
     }
