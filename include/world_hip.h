@@ -343,6 +343,23 @@ int wh_modify_duration(wh_ctx* ctx, void* stream, const wh_batch* b, const doubl
 int wh_pcm16_to_f64(wh_ctx* ctx, void* stream, const int16_t* pcm, int64_t n, double* x);
 int wh_f64_to_pcm16(wh_ctx* ctx, void* stream, const double* y, int64_t n, int16_t* pcm);
 
+/* ---- Polyphase resampling in front of the analysis: replaces scipy.signal.resample_poly  (example/prosody.py:16-19) ---- */
+/* y = resample_poly(x, up, down) per utterance of a ragged batch, bit for bit with scipy's defaults (window=('kaiser',
+ * 5.0), padtype='constant', cval=None): upfirdn's loop — output j sums x[k] * h_trans_flip[(j*down) % up][.] over
+ * k = (j*down)/up - P + 1 .. (j*down)/up in ascending order, each product rounded on its own, taps of k outside the
+ * signal skipped — and output i of utterance u is upfirdn's j = i + h_pre_remove[u].
+ *   h_in_off[n_utt+1], h_out_off[n_utt+1] (HOST, int64, monotone): sample offsets into x and y; n_out of utterance u
+ *     must be ceil(n_in * up / down) (an empty utterance gives an empty output);
+ *   h_up[u], h_down[u] (HOST): positive, at most 4096 (pass them reduced by their gcd, as resample_poly does);
+ *   h_filters[n_filters] (HOST): the padded FIRs as resample_poly builds them (firwin(2*half+1, 1/max(up, down),
+ *     window) * up behind n_pre_pad zeros and ahead of n_post_pad zeros); utterance u uses h_filters[h_filt_off[u] ..
+ *     + h_filt_len[u]), and h_pre_remove[u] = (half + n_pre_pad) / down.  P = ceil(h_filt_len / up).  The phase tables
+ *     are built here and cached in the context's bounded table cache by content.
+ * x, y: DEVICE.  Asynchronous (the first call with a new filter uploads its table synchronously). */
+int wh_resample_poly(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_in_off, const int64_t* h_out_off,
+                     const int32_t* h_up, const int32_t* h_down, const int64_t* h_filt_off, const int64_t* h_filt_len,
+                     const int64_t* h_pre_remove, const double* h_filters, int64_t n_filters, const double* x, double* y);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,9 @@ SIGNATURES = {
     "wh_f64_to_pcm16": (_int, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
     "wh_swipe": (_int, [_vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp]),
     "wh_requiem_seeds": (_int, [_vp, _vp, _dbl, _int, ctypes.c_int64, _int, ctypes.c_uint64, _vp, _vp, _vp]),
+    "wh_resample_poly": (_int, [_vp, _vp, _int, _c_i64p, _c_i64p, ctypes.POINTER(ctypes.c_int32),
+                                ctypes.POINTER(ctypes.c_int32), _c_i64p, _c_i64p, _c_i64p, ctypes.POINTER(_dbl),
+                                ctypes.c_int64, _vp, _vp]),
 }
 
 _lib = None

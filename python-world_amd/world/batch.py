@@ -633,6 +633,67 @@ class WorldBatch:
         return batch, x_d, tp_d
 
     @_on_lane_stream
+    def resample_device(self, x_d, offsets, fs_in, fs_out):
+        """scipy.signal.resample_poly(x, fs_out, fs_in) of every utterance of a resident ragged buffer (utterance u is
+        x_d[offsets[u]:offsets[u+1]]), bit for bit, as the reference's callers resample before the analysis
+        (example/prosody.py:16-19).  ``fs_in``: one integer rate or one per utterance.  Works on waveforms before an
+        encode and on decode_device's output before to_pcm16.  Returns (y_d, y_off) with y_off a host int64 array."""
+        from .resample import rates_ratio, resample_device
+
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(offsets) - 1
+        fs_in = np.broadcast_to(np.asarray(fs_in), (n,))
+        ratios = [rates_ratio(f, fs_out) for f in fs_in]
+        return resample_device(self.rt, x_d, offsets, [r[0] for r in ratios], [r[1] for r in ratios])
+
+    @_on_lane_stream
+    def upload_resampled(self, xs, fs_in, fs_out, frame_period=5, swipe_grid=False):
+        """upload() of utterances recorded at their own rates, resampled on the device to ``fs_out`` (resample_device):
+        ``xs`` are float64 arrays, or int16 PCM (scaled by 1 / (2**15 - 1) on the device first, as upload_pcm16 does);
+        ``fs_in`` one rate or one per utterance.  Only the source samples cross PCIe.  Returns (batch, x_d, tp_d) at
+        ``fs_out``, ready for encode_device; ``swipe_grid`` as for upload().  No host copy of the resampled waveform exists, so Harvest sizes its
+        crossing lists without ``batch.flat_samples``: a checked encode_device repeats itself where they overflow, an
+        asynchronous one is settled with settle_encode when it comes from encode_resampled."""
+        rt = self.rt
+        xs = [np.asarray(x) for x in xs]
+        pcm = [x.dtype == np.int16 for x in xs]
+        if any(pcm) and not all(pcm):
+            raise ValueError("upload_resampled: pass either int16 PCM or float64 arrays, not a mixture")
+        lens = [len(x) for x in xs]
+        in_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        if xs and all(pcm):
+            pcm_d = rt.torch.from_numpy(np.concatenate(xs)).to(rt.device)
+            src_d = rt.empty((int(in_off[-1]),))
+            if in_off[-1] > 0:
+                _hip.check(rt.lib.wh_pcm16_to_f64(rt.ctx, rt.stream(), rt.ptr(pcm_d), int(in_off[-1]), rt.ptr(src_d)))
+        else:
+            src_d = rt.to_device_concat([np.asarray(x, dtype=np.float64) for x in xs])
+        x_d, y_off = self.resample_device(src_d, in_off, fs_in, fs_out)
+        nfs = [_tables.frame_count(int(n), fs_out, frame_period) for n in np.diff(y_off)]
+        batch = rt.make_batch(y_off, np.concatenate([[0], np.cumsum(nfs)]))
+        if swipe_grid:
+            _require_swipe_period(frame_period)
+            tp_h = np.concatenate([np.arange(0, n) * SWIPE_DT for n in nfs]) if nfs else np.zeros(0)
+        else:
+            tp_h = np.concatenate([_tables.frame_times(n, frame_period) for n in nfs]) if nfs else np.zeros(0)
+        tp_d = rt.to_device(tp_h)
+        batch.tp_d, batch.tp_host = tp_d, tp_h
+        return batch, x_d, tp_d
+
+    def encode_resampled(self, xs, fs_in, fs_out, **kw):
+        """encode() of utterances at their own rates: upload_resampled to ``fs_out``, then encode_device at ``fs_out``.
+        An asynchronous Harvest encode (check=False) can be settled with settle_encode like one from encode(); SWIPE' runs on
+        its own 5 ms grid, as in encode()."""
+        if kw.get('f0_method') == 'swipe':
+            kw = dict(kw, frame_period=5)
+        batch, x_d, tp_d = self.upload_resampled(xs, fs_in, fs_out, kw.get('frame_period', 5),
+                                                 swipe_grid=kw.get('f0_method') == 'swipe')
+        enc = self.encode_device(batch, x_d, tp_d, fs_out, **kw)
+        if kw.get('f0_method') == 'harvest' and kw.get('check', True) is not True and kw.get('event_caps') is None:
+            enc._repeat = (batch, x_d, tp_d, fs_out, {k: v for k, v in kw.items() if k not in ('check', 'f0_done')})
+        return enc
+
+    @_on_lane_stream
     def to_pcm16(self, y, y_off):
         """List of per-utterance int16 arrays from decode_device's output, (y * 2**15).astype(int16) evaluated on the
         device (example/prosody.py:57): a quarter of the float64 bytes come back over PCIe."""
