@@ -82,6 +82,10 @@ int wh_bounds_selftest(wh_ctx* ctx, void* stream);
 /* Test hook: the spectral kernels' own log / exp / sincospi (csrc/wh_math.h: a few ulp, a third of the device library's
  * instructions) applied to a DEVICE array: which = 0 log -> out[n], 1 exp -> out[n], 2 (sin, cos)(pi x) -> out[2n]. */
 int wh_math_probe(wh_ctx* ctx, void* stream, int which, const double* in, double* out, int64_t n);
+/* Test hook: the wave-local FFT engine (wh::fft_lds_wave, csrc/wh_device.h) on DEVICE data: `count` unnormalised complex
+ * transforms of n = 512 points, interleaved (re, im) doubles, in -> out; inverse = 1: exp(+2 pi i k j / n), not divided by
+ * n.  (gt, snt): threads per transform group and per workgroup, one of (64, 64), (128, 256), (256, 256). */
+int wh_fft_probe(wh_ctx* ctx, void* stream, int n, int gt, int snt, int inverse, const double* in, double* out, int64_t count);
 /* The same flags without a host wait, for callers that keep a pipeline of batches in flight:
  *   wh_flags_post — enqueue (one 16-lane kernel on `stream`) the publication of the flags raised by everything before
  *     it on the stream to a pinned host word per flag, and clear them on the device (discard != 0: clear them

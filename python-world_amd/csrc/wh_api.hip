@@ -153,7 +153,7 @@ static thread_local int64_t g_bounds_last[4] = {0, 0, 0, 0};
 
 extern "C" {
 
-int wh_version(void) { return 107; }
+int wh_version(void) { return 108; }
 const char* wh_last_error(void) { return g_last_error.c_str(); }
 
 int wh_device_count(int* count) {
@@ -304,6 +304,49 @@ int wh_math_probe(wh_ctx* ctx, void* stream, int which, const double* in, double
   if (n == 0) return 0;
   hipLaunchKernelGGL(math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, which, in, out, (long long)n);
   WH_LAUNCH_CHECK("math_probe_kernel");
+  return 0;
+}
+
+// The wave-local transform engine (wh::fft_lds_wave) on caller data: count transforms of 512 complex points, SNT / GT of them
+// per workgroup, each on the first wave of its GT-thread group — the shapes response_kernel<1024> runs (GT 128 and 256 in a
+// 256-thread workgroup) and a one-wave workgroup.
+extern "C++" {  // (a template, inside the C-ABI block)
+template <int GT, int SNT>
+static __global__ __launch_bounds__(SNT) void fft_probe_kernel(const double2* __restrict__ in, double2* __restrict__ out,
+                                                              const double2* __restrict__ tw_base, long long count, int inv) {
+  constexpr int N = 512;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int g = threadIdx.x / GT, t = threadIdx.x % GT;
+  const long long b = (long long)blockIdx.x * (SNT / GT) + g;
+  const wh::ckp<double2> lds = wh::ck_make(reinterpret_cast<double2*>(smem), (long long)N * (SNT / GT), wh::WH_CK_LDS_OTHER);
+  const wh::ckp<double2> s = wh::ck_sub(lds, (long long)g * N, N, wh::WH_CK_LDS_MAIN);
+  const wh::ckp<const double2> tw = wh::ck_make(tw_base, WH_TWIDDLE_ENTRIES, wh::WH_CK_TWIDDLE);
+  for (int i = t; i < N; i += GT) s[i] = b < count ? in[b * N + i] : make_double2(0.0, 0.0);
+  __syncthreads();
+  if (inv) wh::fft_lds_wave<N, true, GT, SNT>(s, tw + N);  // (workgroup-uniform branch)
+  else wh::fft_lds_wave<N, false, GT, SNT>(s, tw + N);
+  if (b < count)
+    for (int i = t; i < N; i += GT) out[b * N + i] = s[i];
+}
+}  // extern "C++"
+int wh_fft_probe(wh_ctx* ctx, void* stream, int n, int gt, int snt, int inverse, const double* in, double* out, int64_t count) {
+  if (!ctx || !in || !out || count < 0 || n != 512 || (inverse != 0 && inverse != 1))
+    return wh::fail_msg("wh_fft_probe", "bad argument");
+  WH_ENTER(ctx);
+  if (count == 0) return 0;
+  const hipStream_t st = (hipStream_t)stream;
+  const double2* a = reinterpret_cast<const double2*>(in);
+  double2* o = reinterpret_cast<double2*>(out);
+  auto launch = [&](auto kernel, int g, int t) {
+    const int per = t / g;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((count + per - 1) / per)), dim3(t), sizeof(double2) * 512 * per, st, a, o,
+                       (const double2*)ctx->d_twiddle, (long long)count, inverse);
+  };
+  if (gt == 64 && snt == 64) launch(fft_probe_kernel<64, 64>, 64, 64);
+  else if (gt == 128 && snt == 256) launch(fft_probe_kernel<128, 256>, 128, 256);
+  else if (gt == 256 && snt == 256) launch(fft_probe_kernel<256, 256>, 256, 256);
+  else return wh::fail_msg("wh_fft_probe", "shape not built (gt, snt): (64, 64), (128, 256), (256, 256)");
+  WH_LAUNCH_CHECK("fft_probe_kernel");
   return 0;
 }
 

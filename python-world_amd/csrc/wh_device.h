@@ -595,6 +595,22 @@ __device__ __forceinline__ void fft_lds(ckp<double2> s, ckp<const double2> tw) {
   fft_passes<N, NT, 1, INV, SNT, MAXR>(s, tw);
 }
 
+// The same transform by ONE wave of a GT-thread group: a 512-point transform is exactly 64 radix-8 butterflies per
+// pass, so the wave that the workgroup-wide plan (fft_lds<512, .., 128, ..>) left alone with the butterflies anyway
+// owns all of them, and its passes are ordered by wavefront fences instead of two s_barrier each (6 per transform).
+// The group's other waves go straight to the one barrier at the end, which spans SNT threads like fft_lds's and makes
+// the result visible to all of them.  Where fft_lds<N, INV, GT> runs 8-8-8 (GT <= 128 at N = 512) this is the same plan,
+// layout and twiddles: the same bits; a 256-thread group's 4-4-4-4-2 plan rounds differently (ulps).
+// Feature macro for tools/ubench/fft_plans.hip only: its -DFFT_HEADER A/B builds against older revisions of this header,
+// which lack fft_lds_wave; nothing in the library tests it.
+#define WH_HAVE_FFT_WAVE 1
+template <int N, bool INV, int GT, int SNT = GT>
+__device__ __forceinline__ void fft_lds_wave(ckp<double2> s, ckp<const double2> tw) {
+  static_assert(N / 8 <= WH_WAVE && GT % WH_WAVE == 0 && SNT % GT == 0, "one wave must own a pass's butterflies");
+  if ((WH_TID & (GT - 1)) < WH_WAVE) fft_lds<N, INV, WH_WAVE, WH_WAVE>(s, tw);
+  sync_lds<SNT>();
+}
+
 // The same transform with the input still in registers: x[q] = element tid + q*NT, q < N/NT (the layout a
 // thread-strided producer loop leaves behind).  When N >= R*NT (R the first radix) those are exactly the operands
 // of this thread's first-pass butterflies, so the input never makes the trip through LDS.  The buffer must be

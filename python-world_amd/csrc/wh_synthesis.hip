@@ -921,10 +921,21 @@ __device__ __attribute__((noinline)) double2 sincospi_call(double x) {
 //       complex product per bin, and the four passes over the half spectrum become one.
 // `mul(k, E)`: what the minimum-phase bin k (0 <= k <= N/2) is multiplied with before the inverse transform — identity
 // for the pulse responses, the excitation frame's spectrum in the Requiem filter (synthesisRequiem.py:112-118).
+// The chain's three 512-point transforms (N = 1024, the 16 kHz shape): WAVE puts each on one wave of its GT-thread group
+// (wh::fft_lds_wave: one barrier per transform where the workgroup-wide plan takes six; the voiced chains' plan and bits
+// are unchanged, an unvoiced pulse's single chain goes from 4-4-4-4-2 on two waves to 8-8-8 on one).  Other lengths and
+// the Requiem filter keep the workgroup-wide plans.
+template <int M, bool INV, int GT, int FT, bool WAVE>
+__device__ __forceinline__ void mp_fft(wh::ckp<double2> zb, wh::ckp<const double2> tw) {
+  if constexpr (WAVE) wh::fft_lds_wave<M, INV, GT, FT>(zb, tw);
+  else wh::fft_lds<M, INV, GT, FT>(zb, tw);
+}
+template <int N>
+constexpr bool resp_wave_fft() { return N == 1024; }
 struct SpectrumIdentity {
   __device__ __forceinline__ double2 operator()(int, double2 e) const { return e; }
 };
-template <int N, int GT, class Mul = SpectrumIdentity>
+template <int N, int GT, bool WAVE = false, class Mul = SpectrumIdentity>
 __device__ __forceinline__ void min_phase_response(wh::ckp<double2> zb, wh::ckp<const double2> tw_base, double delay_pi, Mul mul = Mul()) {
 #if WH_SYN_CONTRACT
 #pragma clang fp contract(fast)
@@ -938,7 +949,7 @@ __device__ __forceinline__ void min_phase_response(wh::ckp<double2> zb, wh::ckp<
 #if defined(WH_RESP_ABLATE_T1) && WH_RESP_ABLATE_T1
   wh::sync<FT>();  // TIMING EXPERIMENT ONLY (wrong results): the chain's first transform costs nothing — twice the upper
 #else              // bound of packing the two chains' real-even first transforms into one (DCT-I)
-  wh::fft_lds<M, false, GT, FT>(zb, tw_base + M);
+  mp_fft<M, false, GT, FT, WAVE>(zb, tw_base + M);
 #endif
   {
     double ck[PP], cm[PP];
@@ -977,7 +988,7 @@ __device__ __forceinline__ void min_phase_response(wh::ckp<double2> zb, wh::ckp<
     for (int n = 1 + gt; n < M; n += GT) zr[n] = 0.0;
     wh::sync<FT>();
   }
-  wh::fft_lds<M, false, GT, FT>(zb, tw_base + M);
+  mp_fft<M, false, GT, FT, WAVE>(zb, tw_base + M);
 #pragma unroll 1
   for (int k = gt; k <= M / 2; k += GT) {
     const double2 a = zb[k], b = zb[M - k];
@@ -1021,7 +1032,7 @@ __device__ __forceinline__ void min_phase_response(wh::ckp<double2> zb, wh::ckp<
     if (k != 0) zb[M - k] = make_double2(er + oi, orr - ei);
   }
   wh::sync<FT>();
-  wh::fft_lds<M, true, GT, FT>(zb, tw_base + M);
+  mp_fft<M, true, GT, FT, WAVE>(zb, tw_base + M);
 }
 
 // padded index of the aperiodic response for the register-tiled convolution: 2 doubles of padding every 32
@@ -1275,12 +1286,12 @@ __device__ __forceinline__ void response_pulse(const RespArgs& A, const PulseRec
   const double coef_pi = 2.0 * fs / N;  // coefficient = 2*pi*fs/N (synthesis.py:59), kept in units of pi
   if (NG == 2 && voiced) {
     const int g = WH_TID / GT;
-    min_phase_response<N, GT>(g == 0 ? zbA : zbP, tw_base, g == 0 ? 0.0 : coef_pi * shift);
+    min_phase_response<N, GT, resp_wave_fft<N>()>(g == 0 ? zbA : zbP, tw_base, g == 0 ? 0.0 : coef_pi * shift);
   } else {
     // an unvoiced pulse has no periodic response (synthesis.py:69-75): one chain, on all the threads — 40 % of the
     // pulses of speech-like input (the 500 Hz default rate of unvoiced stretches) do half the transform work
-    min_phase_response<N, FT>(zbA, tw_base, 0.0);
-    if (voiced) min_phase_response<N, FT>(zbP, tw_base, coef_pi * shift);
+    min_phase_response<N, FT, resp_wave_fft<N>()>(zbA, tw_base, 0.0);
+    if (voiced) min_phase_response<N, FT, resp_wave_fft<N>()>(zbP, tw_base, coef_pi * shift);
   }
   RSTAGE_MARK(2)
   // zrA[n] = N * aperiodic response, zrP[n] = N * periodic response (both before fftshift)

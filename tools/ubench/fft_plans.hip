@@ -32,7 +32,8 @@ constexpr int kReps = 8;     // transforms per buffer per workgroup
 
 // One workgroup: SNT threads, SNT / NT buffers of N points, kReps transforms each.  Transform 0 of the first kInputs
 // buffers is written out for the check; the rest feed a checksum so that nothing is optimised away.
-template <int N, int NT, int SNT, int MINW, bool REGFED>
+// WAVE: wh::fft_lds_wave — the first wave of each NT-thread group runs the transform, one SNT-wide barrier at the end.
+template <int N, int NT, int SNT, int MINW, bool REGFED, bool WAVE = false>
 __global__ __launch_bounds__(SNT, MINW) void fft_case(const double2* __restrict__ in, const double2* __restrict__ tw,
                                                       double2* __restrict__ out, double* __restrict__ sink, int n_buf) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -49,6 +50,10 @@ __global__ __launch_bounds__(SNT, MINW) void fft_case(const double2* __restrict_
 #pragma unroll
       for (int q = 0; q < N / NT; ++q) v[q] = x[tid + q * NT];
       wh::fft_lds_from_regs<N, false, NT, 8>(v, s, t + N);
+    } else if constexpr (WAVE) {
+      for (int i = tid; i < N; i += NT) s[i] = x[i];
+      __syncthreads();
+      wh::fft_lds_wave<N, false, NT, SNT>(s, t + N);
     } else {
       for (int i = tid; i < N; i += NT) s[i] = x[i];
       __syncthreads();
@@ -62,7 +67,7 @@ __global__ __launch_bounds__(SNT, MINW) void fft_case(const double2* __restrict_
   if (b < n_buf) sink[(size_t)b * NT + tid] = acc;
 }
 
-template <int N, int NT, int SNT, int MINW, bool REGFED>
+template <int N, int NT, int SNT, int MINW, bool REGFED, bool WAVE = false>
 int run_case(const char* name, const double2* d_tw, const std::vector<double2>& h_in, const double2* d_in) {
   constexpr int PER_WG = SNT / NT;
   const int n_transforms = 131072;
@@ -73,7 +78,7 @@ int run_case(const char* name, const double2* d_tw, const std::vector<double2>& 
   CK(hipMalloc(&d_out, sizeof(double2) * N * kInputs));
   CK(hipMalloc(&d_sink, sizeof(double) * n_buf * NT));
   const size_t lds = sizeof(double2) * N * PER_WG;
-  auto k = fft_case<N, NT, SNT, MINW, REGFED>;
+  auto k = fft_case<N, NT, SNT, MINW, REGFED, WAVE>;
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
@@ -179,6 +184,13 @@ int main() {
     if (N == 512) {
       rc |= run_case<512, 128, 128, 6, false>("cheaptrick 512 (ct_minw)", d_tw, hin, d_in);
       rc |= run_case<512, 128, 256, 4, false>("response 512 x 2 buffers", d_tw, hin, d_in);
+#ifdef WH_HAVE_FFT_WAVE
+      rc |= run_case<512, 64, 64, 4, false>("512 one wave per workgroup", d_tw, hin, d_in);
+      rc |= run_case<512, 128, 128, 6, false, true>("cheaptrick 512 wave-local", d_tw, hin, d_in);
+      rc |= run_case<512, 128, 256, 4, false, true>("response 512 wave-local x 2 buffers", d_tw, hin, d_in);
+      rc |= run_case<512, 256, 256, 4, false>("response 512 unvoiced (4-4-4-4-2)", d_tw, hin, d_in);
+      rc |= run_case<512, 256, 256, 4, false, true>("response 512 unvoiced wave-local", d_tw, hin, d_in);
+#endif
     }
     CK(hipFree(d_in));
   }
