@@ -294,6 +294,26 @@ int wh_feature_matmul_tagged(wh_ctx* ctx, void* stream, const double* a, int64_t
 /* get_context (main.py:360-365): out[i][j*d + c] = x[clamp(i + j - w, 0, n_rows-1)][c], j = 0..2w.  DEVICE pointers. */
 int wh_context_frames(wh_ctx* ctx, void* stream, const double* x, int64_t n_rows, int d, int w, double* out);
 
+/* ---- Manifold vocoder: the Dense stacks of World.encode_vae  (world/main.py:367-384) ------------------------------- */
+/* One launch runs n_layers Dense layers (y = act(x W + b)) over n_rows rows; the activations stay on chip.
+ *   x (DEVICE, frame-major, row stride ldx >= d): the input rows.  The first layer sees row i as get_context does
+ *     (main.py:360-365): columns j*d + c = x[clamp(i + j - window)][c] - h_in_shift[c], j = 0..2 window, with the clamp
+ *     to the row's own segment [h_seg_off[u], h_seg_off[u+1]) (HOST, int64, n_seg + 1 entries from 0 to n_rows), so that
+ *     context never crosses an utterance.  h_in_shift (HOST, d doubles) may be NULL: no shift.  (2 window + 1) d <= 2048.
+ *   h_units[l], h_act[l] (HOST): layer widths (<= 256 except the last) and activations, 0 linear, 1 relu, 2 tanh,
+ *     3 sigmoid.  h_w (HOST): the layers' kernels [in_l][units_l] row-major, one after the other (in_0 = (2 window + 1) d,
+ *     in_l = units_{l-1}); h_b (HOST): their biases.  Non-finite values are refused.
+ *   The last layer computes only its columns [out_col0, out_col0 + n_out) (n_out <= 256), adds h_out_shift[n_out] (HOST,
+ *     may be NULL) and writes out[i*ldo + n] (DEVICE).  tap_layer in [0, n_layers - 1) also writes that layer's output to
+ *     tap_out[i*ld_tap + n] (DEVICE); tap_layer < 0: none.  tap_f32 != 0 rounds the tap layer's output to float32, in
+ *     tap_out and as the next layer's input (Keras' encoder.predict hands the decoder a float32 latent).
+ *   Every row's result is independent of the other rows of the launch.  table_tag != 0 promises that every call with
+ *   this tag (and the same shapes) passes the same h_w / h_b: the padded FP64 copy is then uploaded once and looked up. */
+int wh_dense_stack(wh_ctx* ctx, void* stream, const double* x, int64_t n_rows, int d, int64_t ldx, const int64_t* h_seg_off,
+                   int n_seg, int window, const double* h_in_shift, int n_layers, const int* h_units, const int* h_act,
+                   const double* h_w, const double* h_b, int out_col0, int n_out, int tap_layer, double* tap_out,
+                   int64_t ld_tap, int tap_f32, const double* h_out_shift, double* out, int64_t ldo, uint64_t table_tag);
+
 /* ---- SWIPE': replaces swipe()  (world/swipe.py:9-105; f0_method='swipe', world/main.py:45-46,134-135) ---------- */
 /* One entry of the window-size table (HOST): candidates [j0, j0+n_c) of the candidate set use window size ws with
  * hop `hop` (= ws - noverlap of the reference's specgram call, swipe.py:35-38). */

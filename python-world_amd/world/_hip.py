@@ -78,6 +78,9 @@ SIGNATURES = {
     "wh_feature_matmul_tagged": (_int, [_vp, _vp, _vp, ctypes.c_int64, _int, ctypes.c_int64, _int, _vp, _dbl, _vp, _int, _int,
                                         _vp, ctypes.c_int64, ctypes.c_uint64]),
     "wh_context_frames": (_int, [_vp, _vp, _vp, ctypes.c_int64, _int, _int, _vp]),
+    "wh_dense_stack": (_int, [_vp, _vp, _vp, ctypes.c_int64, _int, ctypes.c_int64, _c_i64p, _int, _int, _vp, _int, _vp, _vp,
+                               _vp, _vp, _int, _int, _int, _vp, ctypes.c_int64, _int, _vp, _vp, ctypes.c_int64,
+                               ctypes.c_uint64]),
     "wh_warp_spectrum": (_int, [_vp, _vp, _vp, ctypes.c_int64, _int, _vp, _vp, _vp]),
     "wh_modify_duration": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
     "wh_pcm16_to_f64": (_int, [_vp, _vp, _vp, ctypes.c_int64, _vp]),

@@ -308,6 +308,32 @@ class BatchEncoding:
         from .features import mcep_device
         return mcep_device(self.rt, self.spectrogram, n0, self.fs, lowhz, highhz)
 
+    # ---- the manifold vocoder on the resident spectrogram (world/main.py:367-384; world/manifold.py) -------------
+    def vae(self, encoder, decoder, mean, n0=40, window=0, lowhz=0, highhz=8000):
+        """encode_mcep (n0 coefficients) of every frame, then the VAE's encoder and decoder in one launch on
+        coefficients 1..n0-1, context per utterance (it never crosses one).  Returns (Z_d, Y_d): the latent [F][latent]
+        (float32 values, as Keras hands them on) and the decoded coefficients 1..n0-1 plus ``mean``, [F][n0-1]."""
+        return self._vae(encoder, decoder, mean, n0, window, lowhz, highhz)[1:]
+
+    def with_vae_spectrogram(self, encoder, decoder, mean, n0=40, window=0, lowhz=0, highhz=8000):
+        """A new encoding that shares this one's f0, vuv and aperiodicity and whose spectrogram is the manifold-vocoded
+        one: decode_mcep(energy | VAE(MCEP), fft_size) (test/spectralFeatures.py's flow), all on the device.
+        WorldBatch.decode_device synthesises it."""
+        from .features import imcep_device
+        mc, _, y_d = self._vae(encoder, decoder, mean, n0, window, lowhz, highhz)
+        cep = self.rt.torch.cat([mc[:, :1], y_d], dim=1).contiguous()
+        spec = imcep_device(self.rt, cep, self.fft_size)
+        return BatchEncoding(self.rt, self.batch, self.fs, self._tp, self.f0, self.vuv, spec, self.aperiodicity,
+                             self.fft_size, self.is_requiem, self.frame_period, tp_host=self.tp_host)
+
+    def _vae(self, encoder, decoder, mean, n0, window, lowhz, highhz):
+        from .features import mcep_device
+        from .manifold import vae_device
+        mc = mcep_device(self.rt, self.spectrogram, n0, self.fs, lowhz, highhz)
+        z_d, y_d = vae_device(self.rt, mc[:, 1:], encoder, decoder, window, mean,
+                              seg_off=np.asarray(self.batch.frame_off, dtype=np.int64))
+        return mc, z_d, y_d
+
     def to_dicts(self, want_ps=False, lazy=False):
         """List of per-utterance dicts with the reference's keys and (bins, frames) layouts.  ``want_ps``: include
         encode()'s 'ps spectrogram' (fft_size, frames) complex128 (world/main.py:149) — the encoding must have been made

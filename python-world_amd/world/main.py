@@ -1,9 +1,9 @@
 """`World` facade: the class, method names, argument order / defaults and result-dict keys of the reference's
 world/main.py:26-214, with every stage running on the MI355X through libworld_hip.so.
 
-The analysis/synthesis path and the spectral feature heads that follow encode() (mel filterbank energies, mel-cepstrum
-and its inverse, context stacking: world/features.py) are provided; the reference's plotting and Keras/VAE glue
-(draw, encode_vae) are not part of this build.
+The analysis/synthesis path, the spectral feature heads that follow encode() (mel filterbank energies, mel-cepstrum
+and its inverse, context stacking: world/features.py) and the manifold vocoder's networks (encode_vae:
+world/manifold.py) are provided; the reference's plotting (draw) is not part of this build.
 """
 import logging
 import os
@@ -15,6 +15,7 @@ from . import cheaptrick as _ct
 from . import d4c as _d4c
 from . import d4cRequiem as _d4cr
 from . import features as _feat
+from . import manifold as _man
 from . import dio as _dio
 from . import get_seeds_signals as _seeds
 from . import harvest as _hv
@@ -133,6 +134,23 @@ def _check_decodable(dats):
                 k0 = k
             elif k != k0:
                 raise ValueError("dict %d: spectrogram of %d bins in a batch of %d" % (n, k, k0))
+
+
+def _vae_args(x, energy, n0, mean, window):
+    """encode_vae / decode_vae's arguments, checked before anything is touched: (energy, mean as n0-1 values, window)."""
+    n0, window = int(n0), int(window)
+    if np.ndim(x) != 2:
+        raise ValueError("encode_vae: the input must be (frames, coefficients), got shape %s" % (np.shape(x),))
+    energy = np.asarray(energy, dtype=np.float64).reshape(-1)
+    if energy.shape[0] != x.shape[0]:
+        raise ValueError("encode_vae: energy has %d values for %d frames" % (energy.shape[0], x.shape[0]))
+    if n0 < 2 or window < 0:
+        raise ValueError("encode_vae: n0 must be >= 2 and window >= 0")
+    try:
+        m = np.ascontiguousarray(np.broadcast_to(np.asarray(mean, dtype=np.float64), (n0 - 1,)))
+    except ValueError:
+        raise ValueError("encode_vae: mean must broadcast to the %d coefficients, got shape %s" % (n0 - 1, np.shape(mean)))
+    return energy, n0, m, window
 
 
 class World(object):
@@ -394,6 +412,48 @@ class World(object):
 
     def get_context(self, X, w=5):
         return _feat.get_context(X, w)
+
+    # ---- manifold vocoder (world/main.py:367-384; world/manifold.py) ----------------------------------------------
+    def encode_vae(self, Xc, energy, encoder, decoder, window, n0, batch_size, mean):
+        """MCEP -> latent -> MCEP through the VAE's encoder and decoder (world/main.py:367-384), both networks in one
+        device launch, FP64 throughout (the reference's Keras runs float32: results differ by float32 rounding).
+
+        ``Xc``: (N, n0-1) MCEP without the energy column; ``energy``: (N,) column 0.  ``encoder`` / ``decoder``: each a
+        world.manifold.DenseStack, a Keras-like model or the path of a Keras HDF5 file.  ``batch_size`` is accepted and
+        ignored (the whole input is one launch).  As in the reference, ``Xc -= mean`` mutates the caller's array.
+        Returns (Zc, Yc): the latent as float32 (Keras predict's dtype) and (N, n0) float64 MCEP with ``energy`` in
+        column 0.  The latent goes on to the decoder rounded to float32, as between Keras' two predict calls."""
+        assert Xc.shape[1] == n0 - 1
+        x = np.array(Xc, dtype=np.float64)  # the kernel subtracts the mean itself, with the same rounding
+        args = _vae_args(x, energy, n0, mean, window)
+        Xc -= mean
+        return self._vae(x, *args, encoder=encoder, decoder=decoder)
+
+    def decode_vae(self, Zc, energy, decoder, window, n0, mean):
+        """Extension (not in the reference): the decoder half of encode_vae on a latent ``Zc`` (N, latent), e.g. one
+        edited for a conversion.  Returns Yc (N, n0) as encode_vae does; decode_vae(encode_vae(...)[0], ...) gives
+        encode_vae's Yc bit for bit."""
+        z = np.asarray(Zc)
+        return self._vae(z, *_vae_args(z, energy, n0, mean, window), decoder=decoder)[1]
+
+    @_hip.serialised
+    def _vae(self, x, energy, n0, m, window, encoder=None, decoder=None):
+        n = x.shape[0]
+        dec = _man.as_stack(decoder)
+        enc = _man.as_stack(encoder) if encoder is not None else None
+        zc = np.zeros((n, enc.units[-1] if enc is not None else x.shape[1]), dtype=np.float32)
+        yc = np.zeros((n, n0))
+        yc[:, 0] = energy
+        if n:
+            rt = _hip.Runtime.get()
+            x_d = rt.to_device(np.ascontiguousarray(x, dtype=np.float64))
+            if enc is not None:
+                z_d, y_d = _man.vae_device(rt, x_d, enc, dec, window, m)
+                zc = z_d.cpu().numpy().astype(np.float32)
+            else:
+                y_d = _man.decode_vae_device(rt, x_d, dec, n0 - 1, window, m)
+            yc[:, 1:] = y_d.cpu().numpy()
+        return zc, yc
 
     # ---- synthesis ----------------------------------------------------------------------------------------------
     def decode(self, dat):
