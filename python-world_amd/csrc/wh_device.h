@@ -610,6 +610,18 @@ __device__ __forceinline__ void fft_lds_wave(ckp<double2> s, ckp<const double2> 
   if ((WH_TID & (GT - 1)) < WH_WAVE) fft_lds<N, INV, WH_WAVE, WH_WAVE>(s, tw);
   sync_lds<SNT>();
 }
+// The same with a job for the waves that own no butterflies: side(i, n) runs on them while the first wave transforms,
+// i = 0 .. n - 1 numbering the n = (SNT / GT) (GT - 64) such threads of the SNT-thread workgroup (all of its groups are
+// expected here at the same time).  side() may write LDS that the transform does not touch — the closing barrier makes
+// it visible with the transform's result — and must not synchronise: the first waves do not go with it.
+template <int N, bool INV, int GT, int SNT, class Side>
+__device__ __forceinline__ void fft_lds_wave(ckp<double2> s, ckp<const double2> tw, Side side) {
+  static_assert(N / 8 <= WH_WAVE && GT % WH_WAVE == 0 && GT > WH_WAVE && SNT % GT == 0, "one wave owns the butterflies, the others the side job");
+  const int gt = WH_TID & (GT - 1);
+  if (gt < WH_WAVE) fft_lds<N, INV, WH_WAVE, WH_WAVE>(s, tw);
+  else side((int)(WH_TID / GT) * (GT - WH_WAVE) + gt - WH_WAVE, (SNT / GT) * (GT - WH_WAVE));
+  sync_lds<SNT>();
+}
 
 // The same transform with the input still in registers: x[q] = element tid + q*NT, q < N/NT (the layout a
 // thread-strided producer loop leaves behind).  When N >= R*NT (R the first radix) those are exactly the operands

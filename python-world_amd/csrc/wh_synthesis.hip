@@ -13,6 +13,8 @@
 //                     (synthesis.py:86-116,144-180), excite the aperiodic one with zero-mean noise
 //                     (direct convolution == the reference's truncated fftfilt), and scatter-add into
 //                     y with the reference's clipped-index semantics.
+#include <type_traits>
+
 #include "wh_host.h"
 #include "wh_math.h"
 // response_kernel walks a run of pulses in a loop.  With the plain thread index every per-thread LDS / twiddle address
@@ -50,6 +52,9 @@ namespace {
 #endif
 #ifndef WH_RESP_ABLATE
 #define WH_RESP_ABLATE 0
+#endif
+#ifndef WH_RESP_ROLES
+#define WH_RESP_ROLES 1  // the pulse's noise run on the waves that idle through the chains' first transform (see response_pulse); 0: in front of the chains
 #endif
 #ifndef WH_RESP_CONV8
 #define WH_RESP_CONV8 1  // the noise convolution with eight outputs per thread from N = 2048 up (see response_pulse); 0: four everywhere
@@ -935,8 +940,12 @@ constexpr bool resp_wave_fft() { return N == 1024; }
 struct SpectrumIdentity {
   __device__ __forceinline__ double2 operator()(int, double2 e) const { return e; }
 };
-template <int N, int GT, bool WAVE = false, class Mul = SpectrumIdentity>
-__device__ __forceinline__ void min_phase_response(wh::ckp<double2> zb, wh::ckp<const double2> tw_base, double delay_pi, Mul mul = Mul()) {
+// `side(i, n)`: a job for the waves that a WAVE chain's FIRST transform leaves without butterflies (wh::fft_lds_wave) —
+// the pulse's noise run in response_pulse.  NoSide: they go straight to the transform's barrier.
+struct NoSide {};
+template <int N, int GT, bool WAVE = false, class Mul = SpectrumIdentity, class Side = NoSide>
+__device__ __forceinline__ void min_phase_response(wh::ckp<double2> zb, wh::ckp<const double2> tw_base, double delay_pi, Mul mul = Mul(),
+                                                   Side side = Side()) {
 #if WH_SYN_CONTRACT
 #pragma clang fp contract(fast)
 #endif
@@ -949,7 +958,8 @@ __device__ __forceinline__ void min_phase_response(wh::ckp<double2> zb, wh::ckp<
 #if defined(WH_RESP_ABLATE_T1) && WH_RESP_ABLATE_T1
   wh::sync<FT>();  // TIMING EXPERIMENT ONLY (wrong results): the chain's first transform costs nothing — twice the upper
 #else              // bound of packing the two chains' real-even first transforms into one (DCT-I)
-  mp_fft<M, false, GT, FT, WAVE>(zb, tw_base + M);
+  if constexpr (WAVE && !std::is_same<Side, NoSide>::value) wh::fft_lds_wave<M, false, GT, FT>(zb, tw_base + M, side);
+  else mp_fft<M, false, GT, FT, WAVE>(zb, tw_base + M);
 #endif
   {
     double ck[PP], cm[PP];
@@ -1237,6 +1247,7 @@ __device__ __forceinline__ void response_pulse(const RespArgs& A, const PulseRec
       if (k > 0 && k < N / 2) zrP[N - k] = lv;
     }
   }
+  RSTAGE_MARK(5)
   // ---- noise for this pulse: max(3, noise_size) samples, zero-mean (synthesis.py:93-95) -----------
   const int64_t nd = noise_size > 3 ? noise_size : 3;
   const int64_t noff = rec.noff;
@@ -1247,8 +1258,43 @@ __device__ __forceinline__ void response_pulse(const RespArgs& A, const PulseRec
     }
     return normal_at(philox_key(seed, (uint64_t)u), (uint64_t)(noff + j));
   };
-  double mean;
-  {
+  // Where a chain's transforms run on one wave of its group (resp_wave_fft), the group's other waves have nothing to do
+  // during them: a device-stream run that fits nz (the usual case) is generated THERE, by the waves that idle through the
+  // first transform of the chains, and its mean is taken behind the chains — nothing reads either before the convolution.
+  constexpr bool ROLES = WH_RESP_ROLES && resp_wave_fft<N>();
+  static_assert(!ROLES || NZ / 2 + 1 <= FT, "a run that fits nz is at most one Philox block per thread");
+  const bool side_noise = ROLES && noise == nullptr && nd <= NZ;  // (workgroup-uniform)
+  // Thread i of the n side threads takes Philox block (noff >> 1) + i like thread i of the workgroup does in front of the
+  // chains, so a side wave holds the partial sums of one wave of block_sum's tree: it leaves their sum in scratch[that
+  // wave] (the chains do not touch scratch either), and the mean behind the chains adds the wave sums in wave order.
+  auto noise_side = [&](int i, int n) {
+    if (!side_noise) return;
+    const uint64_t key = philox_key(seed, (uint64_t)u);
+    const int lane = i & 63;
+    const int64_t blk0 = noff >> 1, b1 = (noff + nd - 1) >> 1;
+    for (int c = __builtin_amdgcn_readfirstlane(i - lane); blk0 + c <= b1; c += n) {  // (wave-uniform: wave_sum wants every lane)
+      const int64_t blk = blk0 + c + lane;
+      double part = 0.0;
+      if (blk <= b1) {
+        const double2 z = normal_pair(key, (uint64_t)blk);
+        const int64_t j = 2 * blk - noff;  // -1 .. nd-1, nd <= NZ
+        if (j >= 0) {
+          part += z.x;
+          nz[j] = z.x;
+        }
+        if (j + 1 < nd) {
+          part += z.y;
+          nz[j + 1] = z.y;
+        }
+      }
+      part = wh::wave_sum(part);
+      if (lane == 0) scratch[c >> 6] = part;
+    }
+  };
+  double mean = 0.0;
+  if (side_noise) {
+    wh::sync<FT>();  // the log spectra are visible
+  } else {
     double part = 0.0;
     if (noise) {
       for (int64_t j = WH_TID; j < nd; j += FT) {
@@ -1284,7 +1330,16 @@ __device__ __forceinline__ void response_pulse(const RespArgs& A, const PulseRec
   return;
 #endif
   const double coef_pi = 2.0 * fs / N;  // coefficient = 2*pi*fs/N (synthesis.py:59), kept in units of pi
-  if (NG == 2 && voiced) {
+  if constexpr (ROLES) {
+    // (one wave per chain transforms: waves 1 and 3 of a voiced pulse, waves 1 - 3 of an unvoiced one take the noise run)
+    if (NG == 2 && voiced) {
+      const int g = WH_TID / GT;
+      min_phase_response<N, GT, true>(g == 0 ? zbA : zbP, tw_base, g == 0 ? 0.0 : coef_pi * shift, SpectrumIdentity(), noise_side);
+    } else {
+      min_phase_response<N, FT, true>(zbA, tw_base, 0.0, SpectrumIdentity(), noise_side);
+      if (voiced) min_phase_response<N, FT, true>(zbP, tw_base, coef_pi * shift);
+    }
+  } else if (NG == 2 && voiced) {
     const int g = WH_TID / GT;
     min_phase_response<N, GT, resp_wave_fft<N>()>(g == 0 ? zbA : zbP, tw_base, g == 0 ? 0.0 : coef_pi * shift);
   } else {
@@ -1294,6 +1349,16 @@ __device__ __forceinline__ void response_pulse(const RespArgs& A, const PulseRec
     if (voiced) min_phase_response<N, FT, resp_wave_fft<N>()>(zbP, tw_base, coef_pi * shift);
   }
   RSTAGE_MARK(2)
+  if (side_noise) {
+    // the mean of the run in block_sum's order: the wave sums the side waves left (visible behind the chains' last
+    // barrier), added in wave order.  (A wave whose threads are all behind the run's last block adds 0.0 there: skipped.)
+    const int n_blk = (int)(((noff + nd - 1) >> 1) - (noff >> 1)) + 1;
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < (NZ / 2 + 1 + 63) / 64; ++w)
+      if (w * 64 < n_blk) t += scratch[w];
+    mean = t / (double)nd;
+  }
   // zrA[n] = N * aperiodic response, zrP[n] = N * periodic response (both before fftshift)
   for (int n = WH_TID; n < N; n += FT) rap[rap_index(n)] = zrA[(n + N / 2) & (N - 1)] / N;
   wh::sync<FT>();

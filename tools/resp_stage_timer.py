@@ -30,9 +30,13 @@ for it in range(3):
     torch.cuda.synchronize()
     lib.wh_debug_resp_stages(buf, 1)
 v = np.array(list(buf), dtype=np.float64)
-names = ["setup: pulse look-up, 4 spectral rows, noise, mean", "2 x (log, rFFT, fold, rFFT, exp) + fractional delay",
-         "2 x inverse real FFT", "response reorder + noise convolution", "DC sum + overlap-add atomics"]
-tot = v[:5].sum()
-for n, c in zip(names, v[:5]):
-    print("%-55s %6.1f %%" % (n, 100 * c / tot))
+# slot 5: from the pulse's start to the logs; slot 0: from there to the chains (with the wave roles of the 16 kHz shape the
+# noise run and its mean are no longer here: the run is generated under the chains' first transform, slot 2, and the mean
+# is taken in front of the convolution, slot 3)
+names = {5: "setup: pulse look-up, 4 spectral rows, interpolation, logs", 0: "setup: noise run + mean in front of the chains",
+         2: "minimum-phase chains (3 transforms each)", 3: "response reorder + noise convolution",
+         4: "DC sum + overlap-add into the run's ring"}
+tot = v[:6].sum()
+for i in (5, 0, 2, 3, 4):
+    print("%-60s %6.1f %%  %.3e cycles" % (names[i], 100 * v[i] / tot, v[i]))
 print("total cycles (sum over pulses) %.3e" % tot)
