@@ -132,6 +132,23 @@ int wh_d4c(wh_ctx* ctx, void* stream, const wh_batch* b, const double* x, const 
 /* Number of aperiodicity bands: floor(min(15000, fs/2-interval)/interval) (d4c.py:34, d4cRequiem.py:19). */
 int wh_d4c_bands(double fs, int requiem);
 
+/* ---- Band aperiodicity -> dense aperiodicity: the last step of d4c()  (world/d4c.py:45-59) -------- */
+/* The expansion of a stored band aperiodicity (the reference's 'coarse_ap') into the dense rows that wh_synthesis
+ * reads, without running D4C again:
+ *   out[f][k] = 1 - 1e-12                                                                     where gate[f] == 0 (d4c.py:50)
+ *             = 10 ** (interp(coarse_axis, [-60, coarse[f][:], -1e-12])(k * fs / fft_size) / 20)   otherwise (d4c.py:58-59)
+ * with coarse_axis = [0, fi, 2 fi, ..., nap fi, fs / 2] (d4c.py:45), fi = frequency_interval in Hz, fft_size =
+ * 2 (k_bins - 1).  coarse[n_frames][nap] holds the values as wh_d4c's coarse_ap does (negated dB; a -0.0 stays one),
+ * gate[n_frames] is 0 for the frames D4C's voicing gate rejected (unvoiced ones among them) and non-zero for the others,
+ * out[n_frames][k_bins].  All DEVICE pointers.  The rows are bit for bit the ones wh_d4c writes for the same frames: both
+ * kernels evaluate the interpolation through the same device functions.  1 <= nap <= 8, nap * fi < fs / 2. */
+int wh_aperiodicity_from_bands(wh_ctx* ctx, void* stream, int64_t n_frames, int nap, int k_bins, double fs,
+                               int frequency_interval, const double* coarse, const double* gate, double* out);
+/* gate[f] = 0.0 where row f of wh_d4c's aperiodicity[n_frames][k_bins] is the rejected frame's constant row, 1.0 where it
+ * came from the bands: read from bin 0, which holds 1 - 1e-12 in the first case and 10^(-60/20) in the second. */
+int wh_aperiodicity_gate(wh_ctx* ctx, void* stream, int64_t n_frames, int k_bins, const double* aperiodicity,
+                         double* gate);
+
 /* ---- D4C-Requiem: replaces d4cRequiem()  (world/d4cRequiem.py:9-44) ------------------------- */
 /* fft_size <= 0 selects the reference default 2^ceil(log2(3fs/47+1)).
  * band_aperiodicity[total_frames][wh_d4c_bands(fs,1)+2] in dB (row 0 = -60, last = -1e-12). */

@@ -72,6 +72,8 @@ SIGNATURES = {
                                     _vp, _int, _vp, ctypes.c_int64, _int, _vp, _vp]),
     "wh_d4c": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _int, _vp, _vp]),
     "wh_d4c_bands": (_int, [_dbl, _int]),
+    "wh_aperiodicity_from_bands": (_int, [_vp, _vp, ctypes.c_int64, _int, _int, _dbl, _int, _vp, _vp, _vp]),
+    "wh_aperiodicity_gate": (_int, [_vp, _vp, ctypes.c_int64, _int, _vp, _vp]),
     "wh_d4c_requiem": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _int, _vp]),
     "wh_feature_matmul": (_int, [_vp, _vp, _vp, ctypes.c_int64, _int, ctypes.c_int64, _int, _vp, _dbl, _vp, _int, _int, _vp,
                                  ctypes.c_int64]),

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _hip, _tables
 from .cheaptrick import cheaptrick_device, default_fft_size
-from .d4c import d4c_device
+from .d4c import aperiodicity_gate_device, d4c_device
 from .d4cRequiem import d4c_requiem_device
 from .dio import dio_device
 from .stonemask import stonemask_device
@@ -152,6 +152,9 @@ class BatchEncoding:
         self.spectrogram, self.aperiodicity = spectrogram, aperiodicity
         self.fft_size, self.is_requiem, self.frame_period = fft_size, is_requiem, frame_period
         self._timebase = None  # synthesis time base computed ahead by WorldBatch.encode_device (see timebase_for)
+        # D4C's band aperiodicity [F][nap] ('coarse_ap', world/d4c.py:57) and its voicing gate [F]: kept only when
+        # encode_device(want_coarse=True); what compact() stores instead of the dense aperiodicity
+        self.coarse_ap = self.ap_gate = None
 
     @classmethod
     def from_dicts(cls, rt, dats):
@@ -307,6 +310,18 @@ class BatchEncoding:
         """encode_mcep of every frame of the batch: device tensor [F][n0]."""
         from .features import mcep_device
         return mcep_device(self.rt, self.spectrogram, n0, self.fs, lowhz, highhz)
+
+    def compact(self, n0=40, lowhz=0, highhz=8000, mcep_fs=None):
+        """The compact form of this encoding (world.compact.CompactEncoding), resident: f0 / vuv / frame times, the
+        n0-coefficient mel-cepstrum of the spectrogram (encode_mcep) and D4C's band aperiodicity with its voicing gate —
+        360 B per frame at 16 kHz with n0 = 40 against 8 232 dense.  Needs encode_device(want_coarse=True) (a Requiem
+        encoding already holds bands).  decode_mcep hard-codes 16 kHz (world/main.py:347-355), so other rates raise
+        ValueError; ``n0=None`` keeps the dense spectrogram and codes the aperiodicity only, at every rate.
+        ``mcep_fs=16000``: say explicitly what the reference's feature script does implicitly — it calls
+        encode_mcep(spec, n0) with the default fs = 16000 on its 22.05 kHz example (test/spectralFeatures.py:21,31-33),
+        i.e. warps the bins as if the rate were 16 kHz on both sides; the aperiodicity keeps the true rate."""
+        from .compact import compact_encoding
+        return compact_encoding(self, n0, lowhz, highhz, mcep_fs)
 
     # ---- the manifold vocoder on the resident spectrogram (world/main.py:367-384; world/manifold.py) -------------
     def vae(self, encoder, decoder, mean, n0=40, window=0, lowhz=0, highhz=8000):
@@ -465,7 +480,7 @@ class WorldBatch:
     @_on_lane_stream
     def encode_device(self, batch, x_d, tp_d, fs, f0_method='dio', f0_floor=71, f0_ceil=800, channels_in_octave=2,
                       target_fs=4000, frame_period=5, allowed_range=0.1, fft_size=None, is_requiem=False,
-                      f0_done=None, check=True, want_ps=False, event_caps=None):
+                      f0_done=None, check=True, want_ps=False, event_caps=None, want_coarse=False):
         """world/main.py:106-152 for a resident batch.  tp_d is not modified (a copy is kept in the result).
         ``f0_done``: optional callable invoked once the F0 stage has been enqueued (used to stagger lanes).
         ``check``: True — read the sticky device flags afterwards (synchronises this lane's stream) and raise
@@ -477,7 +492,9 @@ class WorldBatch:
         ``event_caps`` (Harvest): capacities of its zero-crossing lists, see ``world.harvest.harvest_device``.  With
         ``check=True`` a call whose estimate was exceeded (WH_FLAG_EVENT_OVERFLOW: stretches constant up to rounding, e.g.
         digital silence next to signal) is repeated once with the capacities it counted; an asynchronous call reports
-        the condition and the caller repeats it (``event_caps='safe'`` or ``counted_event_caps``)."""
+        the condition and the caller repeats it (``event_caps='safe'`` or ``counted_event_caps``).
+        ``want_coarse``: keep D4C's band aperiodicity as ``enc.coarse_ap`` [F][nap] and its voicing gate as ``enc.ap_gate``
+        [F] (one more small kernel), what ``enc.compact()`` needs; off, the call enqueues what it always did."""
         rt = self.rt
         self._deferred_begin(check, "encode_device")
         if fft_size is not None:
@@ -507,8 +524,10 @@ class WorldBatch:
         spec_d, ps_d = cheaptrick_device(rt, batch, x_d, tp_d, f0_d, vuv_d, fs, ct_fft, want_ps=want_ps)
         if is_requiem:
             ap_d = d4c_requiem_device(rt, batch, x_d, tp_d, f0_d, vuv_d, fs, 0.85, fft_size)
+            coarse_d = gate_d = None
         else:
-            ap_d, _ = d4c_device(rt, batch, x_d, tp_d, f0_d, vuv_d, fs, 0.85, ct_fft)
+            ap_d, coarse_d = d4c_device(rt, batch, x_d, tp_d, f0_d, vuv_d, fs, 0.85, ct_fft, want_coarse=want_coarse)
+            gate_d = aperiodicity_gate_device(rt, ap_d) if want_coarse else None
         if check == 'deferred':
             rt.post_flags()
         elif check:
@@ -521,10 +540,11 @@ class WorldBatch:
                     self._tb_rt.take_flags()
                 return self.encode_device(batch, x_d, tp_d, fs, f0_method, f0_floor, f0_ceil, channels_in_octave, target_fs,
                                           frame_period, allowed_range, fft_size, is_requiem, None, True, want_ps,
-                                          counted_event_caps(rt))
+                                          counted_event_caps(rt), want_coarse)
             rt.raise_for_flags(flags, "encode_device")
         enc = BatchEncoding(rt, batch, fs, tp_d.clone(), f0_d, vuv_d, spec_d, ap_d, ct_fft, is_requiem, frame_period,
                             tp_host=None if tp_host is None else tp_host.copy(), ps_spectrogram=ps_d)
+        enc.coarse_ap, enc.ap_gate = coarse_d, gate_d
         if timebase is not None:
             # join: behind CheapTrick and D4C in stream order, so the overlap has already happened — and the fork is
             # closed inside this call (a caller that captures encode_device alone in a graph gets a well-formed one)

@@ -1,0 +1,269 @@
+"""Compact encodings: what a corpus builder stores instead of the dense analysis tensors — f0, vuv, an n0-coefficient
+mel-cepstrum (the reference's encode_mcep, world/main.py:324-341, as test/spectralFeatures.py:31-33 computes it) and D4C's
+band aperiodicity ('coarse_ap', world/d4c.py:57,62) — produced on the device, stored, reloaded and expanded again on the
+device just before the synthesis, without a dense tensor crossing PCIe.
+
+    enc = wb.encode(xs, 16000, want_coarse=True)        # BatchEncoding, resident
+    ce = enc.compact(n0=40)                              # CompactEncoding, resident: 360 B per frame instead of 8 232
+    ce.to_host().save_npz("batch0.npz")                  # one pinned block over PCIe, one file per batch
+    ...
+    ce = CompactEncoding.load_npz("batch0.npz").to_device(wb.rt)
+    y, y_off = wb.decode_device(ce.expand(wb))           # imcep_device + wh_aperiodicity_from_bands, then the usual decode
+
+The expansion of the spectrum is decode_mcep (world/main.py:343-358), which hard-codes 16 kHz and the 0-8000 Hz warp:
+`compact(n0=...)` therefore refuses other rates; `compact(n0=None)` keeps the dense spectrogram and codes the aperiodicity
+only, at every rate.  Requiem encodings already hold the band form (world/d4cRequiem.py:27-40): it is carried as it is.
+
+save_npz / load_npz and the argument checks are host code and need neither the library nor a GPU."""
+import numpy as np
+
+# tensors of a compact encoding in the order they travel in (all float64, frame-major)
+_FIELDS = ("temporal_positions", "f0", "vuv", "mcep", "spectrogram", "band_ap", "ap_gate")
+
+
+def d4c_band_layout(fs, is_requiem=False):
+    """(frequency_interval, number of bands) of d4c() / d4cRequiem() at ``fs`` (world/d4c.py:25-27,34; d4cRequiem.py:19)."""
+    interval = 2000 if (fs < 16000 and not is_requiem) else 3000
+    return interval, int(np.floor(np.min([15000, fs / 2 - interval]) / interval))
+
+
+def check_compact_args(fs, fft_size, n0, where="compact"):
+    """Raises ValueError for what the spectral side cannot code; touches no device."""
+    if n0 is None:
+        return
+    if fs != 16000:
+        raise ValueError("%s: the mel-cepstrum is expanded by decode_mcep, which hard-codes fs = 16000 Hz and the 0-8000 Hz "
+                         "warp (world/main.py:347-355): fs = %r cannot be rebuilt; compact(n0=None) keeps the dense "
+                         "spectrogram and codes the aperiodicity only" % (where, fs))
+    if int(n0) != n0 or n0 < 2 or n0 > fft_size // 2 + 1:
+        raise ValueError("%s: n0 must be an integer in [2, fft_size // 2 + 1 = %d], got %r" % (where, fft_size // 2 + 1, n0))
+
+
+class CompactEncoding:
+    """A batch of utterances as f0 / vuv / frame times [F], mel-cepstrum [F][n0] (or, ``n0 is None``, the dense spectrogram
+    [F][K]), band aperiodicity [F][nap] with D4C's voicing gate [F] (Requiem: the dB rows [F][nap + 2], no gate) — frames
+    of all utterances one after the other, utterance u being rows frame_off[u]:frame_off[u+1].  The tensors are torch
+    device tensors (``rt`` is the runtime they live on) or, after to_host() / load_npz(), NumPy arrays (``rt is None``)."""
+
+    def __init__(self, rt, fs, fft_size, frame_period, is_requiem, n0, lowhz, highhz, frame_off, temporal_positions, f0,
+                 vuv, mcep, band_ap, ap_gate, spectrogram=None, tp_host=None, mcep_fs=None):
+        self.rt, self.fs, self.fft_size, self.frame_period = rt, fs, int(fft_size), frame_period
+        self.is_requiem, self.n0, self.lowhz, self.highhz = bool(is_requiem), n0, lowhz, highhz
+        self.frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
+        self.temporal_positions, self.f0, self.vuv = temporal_positions, f0, vuv
+        self.mcep, self.spectrogram, self.band_ap, self.ap_gate = mcep, spectrogram, band_ap, ap_gate
+        self.tp_host = tp_host
+        # the rate encode_mcep was told (its `fs` argument): the encoding's own unless compact(mcep_fs=...) said otherwise
+        self.mcep_fs = None if mcep is None else (fs if mcep_fs is None else mcep_fs)
+        self._check_shapes()
+
+    # ---- checks (host) --------------------------------------------------------------------------------------------
+    def _check_shapes(self):
+        fo = self.frame_off
+        if fo.ndim != 1 or len(fo) < 1 or fo[0] != 0 or np.any(np.diff(fo) < 0):
+            raise ValueError("CompactEncoding: frame_off must start at 0 and not decrease")
+        nf = int(fo[-1])
+        for name in ("temporal_positions", "f0", "vuv") + (() if self.is_requiem else ("ap_gate",)):
+            shape = tuple(getattr(self, name).shape)
+            if shape != (nf,):
+                raise ValueError("CompactEncoding: '%s' must hold one value per frame (%d), got shape %s" % (name, nf, shape))
+        if (self.mcep is None) == (self.spectrogram is None):
+            raise ValueError("CompactEncoding: exactly one of mcep and spectrogram is kept")
+        if self.mcep is not None:
+            check_compact_args(self.mcep_fs, self.fft_size, self.n0, "CompactEncoding")
+            want = ("mcep", (nf, int(self.n0)))
+        else:
+            want = ("spectrogram", (nf, self.fft_size // 2 + 1))
+        if tuple(getattr(self, want[0]).shape) != want[1]:
+            raise ValueError("CompactEncoding: '%s' must be %s, got %s" % (want[0], want[1], tuple(getattr(self, want[0]).shape)))
+        _, nap = d4c_band_layout(self.fs, self.is_requiem)
+        bands = nap + 2 if self.is_requiem else nap
+        if nap < 1 or tuple(self.band_ap.shape) != (nf, bands):
+            raise ValueError("CompactEncoding: 'band_ap' must be (%d, %d) at fs = %r, got %s"
+                             % (nf, bands, self.fs, tuple(self.band_ap.shape)))
+
+    @property
+    def n_utt(self):
+        return len(self.frame_off) - 1
+
+    @property
+    def total_frames(self):
+        return int(self.frame_off[-1])
+
+    def _tensors(self):
+        return [(k, getattr(self, k)) for k in _FIELDS if getattr(self, k) is not None]
+
+    def nbytes(self):
+        """Bytes of the per-frame tensors: what to_host() / to_device() move."""
+        return int(sum(int(np.prod(t.shape)) for _, t in self._tensors())) * 8
+
+    def _like(self, rt, arrays, tp_host):
+        return CompactEncoding(rt, self.fs, self.fft_size, self.frame_period, self.is_requiem, self.n0, self.lowhz,
+                               self.highhz, self.frame_off, arrays["temporal_positions"], arrays["f0"], arrays["vuv"],
+                               arrays.get("mcep"), arrays["band_ap"], arrays.get("ap_gate"), arrays.get("spectrogram"),
+                               tp_host=tp_host, mcep_fs=self.mcep_fs)
+
+    # ---- PCIe: one pinned block per direction ----------------------------------------------------------------------
+    def to_host(self):
+        """The same encoding with NumPy arrays: the tensors leave as ONE block through pinned host memory
+        (Runtime.to_host); only the compact tensors cross PCIe."""
+        if self.rt is None:
+            return self
+        rt = self.rt
+        parts = self._tensors()
+        with rt.lock, rt.on_stream():
+            flat = rt.to_host(rt.torch.cat([t.reshape(-1) for _, t in parts]))
+        arrays, at = {}, 0
+        for k, t in parts:
+            n = int(np.prod(t.shape))
+            arrays[k] = flat[at:at + n].reshape(tuple(t.shape))
+            at += n
+        return self._like(None, arrays, arrays["temporal_positions"])
+
+    def to_device(self, rt):
+        """The same encoding resident on ``rt``'s device: one upload through a pinned staging block."""
+        if self.rt is not None:
+            if self.rt.index != rt.index:
+                return self.to_host().to_device(rt)
+            return self
+        parts = self._tensors()
+        with rt.lock, rt.on_stream():
+            flat = rt.to_device_concat([np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for _, a in parts])
+        arrays, at = {}, 0
+        for k, a in parts:
+            n = int(np.prod(a.shape))
+            arrays[k] = flat[at:at + n].view(tuple(a.shape))
+            at += n
+        return self._like(rt, arrays, np.array(self.temporal_positions, dtype=np.float64))
+
+    @classmethod
+    def from_host(cls, host, rt):
+        """``host.to_device(rt)`` for an encoding that to_host() / load_npz() / from_dicts() made."""
+        return host.to_device(rt)
+
+    # ---- expansion ---------------------------------------------------------------------------------------------------
+    def expand(self, world_batch):
+        """BatchEncoding on ``world_batch``'s device, ready for decode_device: spectrogram = imcep_device(mcep, fft_size)
+        (decode_mcep), aperiodicity = wh_aperiodicity_from_bands(band_ap, ap_gate) — D4C's own rows, bit for bit;
+        f0 / vuv / frame times are passed through, and so are a Requiem encoding's band rows."""
+        from .batch import BatchEncoding
+        from .d4c import aperiodicity_from_bands_device
+        from .features import imcep_device
+
+        rt = world_batch.rt
+        ce = self.to_device(rt)
+        with rt.lock, rt.on_stream():
+            batch = rt.make_batch(np.zeros(ce.n_utt + 1, dtype=np.int64), ce.frame_off)
+            spec = ce.spectrogram if ce.mcep is None else imcep_device(rt, ce.mcep, ce.fft_size)
+            if ce.is_requiem:
+                ap = ce.band_ap
+            else:
+                ap = aperiodicity_from_bands_device(rt, ce.band_ap, ce.ap_gate, ce.fs, ce.fft_size)
+        return BatchEncoding(rt, batch, ce.fs, ce.temporal_positions, ce.f0, ce.vuv, spec, ap, ce.fft_size, ce.is_requiem,
+                             ce.frame_period, tp_host=None if ce.tp_host is None else np.array(ce.tp_host))
+
+    # ---- files (host only) -------------------------------------------------------------------------------------------
+    def save_npz(self, path):
+        """One .npz for the batch: the tensors, the per-utterance frame offsets and the parameters."""
+        h = self.to_host()
+        out = {k: np.asarray(a) for k, a in h._tensors()}
+        out["frame_off"] = h.frame_off
+        out["fs"] = np.asarray(h.fs)
+        out["fft_size"] = np.asarray(h.fft_size)
+        out["frame_period"] = np.asarray(np.nan if h.frame_period is None else h.frame_period, dtype=np.float64)
+        out["is_requiem"] = np.asarray(h.is_requiem)
+        out["n0"] = np.asarray(-1 if h.n0 is None else int(h.n0))
+        out["lowhz"] = np.asarray(h.lowhz, dtype=np.float64)
+        out["highhz"] = np.asarray(h.highhz, dtype=np.float64)
+        out["mcep_fs"] = np.asarray(-1 if h.mcep_fs is None else h.mcep_fs)
+        np.savez(path, **out)
+
+    @classmethod
+    def load_npz(cls, path):
+        with np.load(path) as z:
+            g = {k: z[k] for k in z.files}
+        n0 = int(g["n0"])
+        fp = float(g["frame_period"])
+        fs = g["fs"].item()
+        return cls(None, fs, int(g["fft_size"]), None if np.isnan(fp) else (int(fp) if fp == int(fp) else fp),
+                   bool(g["is_requiem"]), None if n0 < 0 else n0, g["lowhz"].item(), g["highhz"].item(), g["frame_off"],
+                   g["temporal_positions"], g["f0"], g["vuv"], g.get("mcep"), g["band_ap"], g.get("ap_gate"),
+                   g.get("spectrogram"), tp_host=g["temporal_positions"],
+                   mcep_fs=None if g["mcep_fs"].item() == -1 else g["mcep_fs"].item())
+
+    # ---- plain dicts (World.encode_compact_batch / decode_compact_batch) ---------------------------------------------
+    def to_dicts(self):
+        """Per utterance a small plain dict: f0, vuv, temporal_positions (frames,), mcep (frames, n0) as encode_mcep
+        returns it, coarse_ap (bands, frames) as d4c() returns it (Requiem: d4cRequiem's 'aperiodicity' rows), ap_gate
+        (frames,) (Requiem: None), fs, fft_size, is_requiem."""
+        h = self.to_host()
+        out = []
+        for u in range(h.n_utt):
+            s = slice(int(h.frame_off[u]), int(h.frame_off[u + 1]))
+            d = {"f0": h.f0[s].copy(), "vuv": h.vuv[s].copy(), "temporal_positions": h.temporal_positions[s].copy(),
+                 "coarse_ap": np.ascontiguousarray(h.band_ap[s].T),
+                 "ap_gate": None if h.ap_gate is None else h.ap_gate[s].copy(),
+                 "fs": h.fs, "fft_size": h.fft_size, "is_requiem": h.is_requiem}
+            if h.mcep is not None:
+                d["mcep"] = h.mcep[s].copy()
+            else:
+                d["spectrogram"] = np.ascontiguousarray(h.spectrogram[s].T)
+            out.append(d)
+        return out
+
+    @classmethod
+    def from_dicts(cls, dats):
+        """Host encoding from to_dicts()-style dicts; raises ValueError for arrays whose lengths disagree and for dicts of
+        mixed fs / fft_size / is_requiem / coefficient count.  Touches no device."""
+        if not dats:
+            raise ValueError("CompactEncoding.from_dicts: no dicts")
+        d0 = dats[0]
+        fs, fft_size, req = d0["fs"], int(d0["fft_size"]), bool(d0["is_requiem"])
+        coded = "mcep" in d0
+        n0 = int(np.shape(d0["mcep"])[1]) if coded and np.ndim(d0["mcep"]) == 2 else None
+        check_compact_args(fs, fft_size, n0 if coded else None, "CompactEncoding.from_dicts")
+        _, nap = d4c_band_layout(fs, req)
+        bands = nap + 2 if req else nap
+        for n, d in enumerate(dats):
+            if d["fs"] != fs or int(d["fft_size"]) != fft_size or bool(d["is_requiem"]) != req:
+                raise ValueError("dict %d: the dicts of one batch must share fs, fft_size and is_requiem (%r / %r / %r "
+                                 "against %r / %r / %r)" % (n, d["fs"], d["fft_size"], bool(d["is_requiem"]), fs, fft_size, req))
+            nf = len(d["f0"])
+            per_frame = [("temporal_positions", (nf,)), ("f0", (nf,)), ("vuv", (nf,)), ("coarse_ap", (bands, nf))]
+            if not req:
+                per_frame.append(("ap_gate", (nf,)))
+            per_frame.append(("mcep", (nf, n0)) if coded else ("spectrogram", (fft_size // 2 + 1, nf)))
+            for key, shape in per_frame:
+                if key not in d or d[key] is None or np.shape(d[key]) != shape:
+                    raise ValueError("dict %d: '%s' must have shape %s, got %s"
+                                     % (n, key, shape, None if d.get(key) is None else np.shape(d[key])))
+        cat = lambda key, t=False: np.concatenate(  # noqa: E731
+            [np.asarray(d[key], dtype=np.float64).T if t else np.asarray(d[key], dtype=np.float64) for d in dats])
+        frame_off = np.concatenate([[0], np.cumsum([len(d["f0"]) for d in dats])])
+        tp = cat("temporal_positions")
+        return cls(None, fs, fft_size, None, req, n0, 0, 8000, frame_off, tp, cat("f0"), cat("vuv"),
+                   cat("mcep") if coded else None, cat("coarse_ap", True), None if req else cat("ap_gate"),
+                   None if coded else cat("spectrogram", True), tp_host=tp)
+
+
+def compact_encoding(enc, n0=40, lowhz=0, highhz=8000, mcep_fs=None):
+    """BatchEncoding.compact: see there."""
+    mcep_fs = enc.fs if mcep_fs is None else mcep_fs
+    check_compact_args(mcep_fs, enc.fft_size, n0, "compact")
+    rt = enc.rt
+    if enc.is_requiem:
+        band_ap, gate = enc.aperiodicity, None
+    else:
+        band_ap, gate = getattr(enc, "coarse_ap", None), getattr(enc, "ap_gate", None)
+        if band_ap is None or gate is None:
+            raise ValueError("compact: this encoding holds no band aperiodicity: encode with want_coarse=True")
+    mcep = spec = None
+    if n0 is None:
+        spec = enc.spectrogram
+    else:
+        from .features import mcep_device
+        with rt.lock, rt.on_stream():
+            mcep = mcep_device(rt, enc.spectrogram, int(n0), mcep_fs, lowhz, highhz)
+    return CompactEncoding(rt, enc.fs, enc.fft_size, enc.frame_period, enc.is_requiem, None if n0 is None else int(n0),
+                           lowhz, highhz, enc.batch.frame_off, enc.temporal_positions, enc.f0, enc.vuv, mcep, band_ap, gate,
+                           spec, tp_host=enc.tp_host, mcep_fs=mcep_fs)

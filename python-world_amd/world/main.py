@@ -357,6 +357,60 @@ class World(object):
             _hand_out(dats[a:b], out, y_off2, copy_out)
         return dats
 
+    # ---- compact encodings (not in the reference's class; world/compact.py) --------------------------------------
+    @_hip.serialised
+    def encode_compact_batch(self, fs, xs, n0=40, devices=None, **encode_kw):
+        """encode_batch() whose results leave the GPU in their compact form: per utterance a small plain dict with f0, vuv,
+        temporal_positions, the n0-coefficient mel-cepstrum 'mcep' (frames, n0) that encode_mcep(spectrogram.T, n0) gives
+        (test/spectralFeatures.py:31-33), D4C's band aperiodicity 'coarse_ap' (bands, frames) (world/d4c.py:57,62) with
+        its voicing gate 'ap_gate' (frames,), fs, fft_size and is_requiem — 360 B per frame at 16 kHz instead of the 8 232
+        of the dense tensors, none of which crosses PCIe.  ``encode_kw``: encode_batch's keywords (Harvest by default).
+        Requiem encodings carry d4cRequiem's band rows under 'coarse_ap' and no gate.  fs must be 16000: decode_mcep
+        hard-codes it (world/main.py:347-355)."""
+        from .batch import WorldBatch
+        from .cheaptrick import default_fft_size
+        from .compact import check_compact_args
+
+        if n0 is None:
+            raise ValueError("encode_compact_batch: n0=None (dense spectrogram kept) is BatchEncoding.compact(n0=None)'s job")
+        fft_size = encode_kw.get('fft_size')
+        check_compact_args(fs, int(fft_size) if fft_size is not None else default_fft_size(fs), n0, "encode_compact_batch")
+        if devices is not None:
+            raise NotImplementedError("encode_compact_batch(devices=...): world.pool hands back one merged encoding per "
+                                      "call, not per-device ones to compact; run one WorldBatch per device instead")
+        xs = list(xs)
+        if not xs:
+            return []
+        kw = dict(encode_kw)
+        kw.setdefault('f0_method', 'harvest')
+        wb = WorldBatch()
+        enc = wb.encode(xs, fs, want_coarse=not kw.get('is_requiem', False), **kw)
+        return enc.compact(n0).to_dicts()
+
+    @_hip.serialised
+    def decode_compact_batch(self, dats, devices=None, **decode_kw):
+        """decode_batch() for encode_compact_batch's dicts: the compact arrays are uploaded as one block, expanded on the
+        device (decode_mcep's kernel for the spectrogram, wh_aperiodicity_from_bands for the aperiodicity — D4C's own
+        rows, bit for bit) and synthesised in one batch; adds 'out' to every dict and returns the list.  ``decode_kw``:
+        keywords of WorldBatch.decode_device (``seed=``, ``noise=``, ...)."""
+        from .batch import WorldBatch
+        from .compact import CompactEncoding
+
+        if not dats:
+            return dats
+        ce = CompactEncoding.from_dicts(dats)  # (every check before anything touches the device)
+        for n, d in enumerate(dats):
+            if len(d['f0']) < 2:
+                raise ValueError("dict %d: fewer than 2 frames" % n)
+        if devices is not None:
+            raise NotImplementedError("decode_compact_batch(devices=...): run one WorldBatch per device instead")
+        wb = WorldBatch()
+        y, y_off = wb.decode_device(ce.expand(wb), **decode_kw)
+        with wb.rt.on_stream():
+            y = wb.rt.to_host(y)
+        _hand_out(dats, y, y_off, True)
+        return dats
+
     # ---- modification (all in place on the dict, like the reference) ------------------------------------------
     def scale_pitch(self, dat, factor):
         """world/main.py:154-162."""
