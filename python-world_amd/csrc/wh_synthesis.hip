@@ -32,12 +32,17 @@ __device__ __forceinline__ unsigned wh_opaque_tid() {
 // -DWH_RESP_STAGE_TIMER: per-stage shader-clock cycles of response_kernel (thread 0 of every workgroup), read with
 // wh_debug_resp_stages (tools/resp_stage_timer.py).
 #ifdef WH_RESP_STAGE_TIMER
-__device__ unsigned long long g_resp_stage[8];
+// Slots 0 - 5: stage cycles (2: the chains of voiced pulses); 6: the chains of unvoiced pulses, 7: those of pairs;
+// 8 - 13 count pulses: voiced, unvoiced with vuv == 0, unvoiced by the aperiodicity rows only, vuv == 0 pulses whose
+// successor in the run could share the chains with them (RSTAGE_COUNT in response_kernel), pairs taken, pulses in all.
+__device__ unsigned long long g_resp_stage[16];
 #define RSTAGE_BEGIN unsigned long long _t0 = __builtin_readcyclecounter();
 #define RSTAGE_MARK(i) { __syncthreads(); if (threadIdx.x == 0) { const unsigned long long _t = __builtin_readcyclecounter(); atomicAdd(&g_resp_stage[i], _t - _t0); _t0 = _t; } }
+#define RSTAGE_COUNT(i) { if (threadIdx.x == 0) atomicAdd(&g_resp_stage[i], 1ull); }
 #else
 #define RSTAGE_BEGIN
 #define RSTAGE_MARK(i)
+#define RSTAGE_COUNT(i)
 #endif
 namespace {
 
@@ -55,6 +60,12 @@ namespace {
 #endif
 #ifndef WH_RESP_ROLES
 #define WH_RESP_ROLES 1  // the pulse's noise run on the waves that idle through the chains' first transform (see response_pulse); 0: in front of the chains
+#endif
+#ifndef WH_RESP_PAIR
+#define WH_RESP_PAIR 1  // two consecutive unvoiced pulses of a run through the two chain buffers side by side (response_pair); 0: one by one
+#endif
+#ifndef WH_RESP_SKIP_AP
+#define WH_RESP_SKIP_AP 1  // a pulse whose record says vuv == 0 does not fetch the aperiodicity rows (see response_pulse); 0: every pulse does
 #endif
 #ifndef WH_RESP_CONV8
 #define WH_RESP_CONV8 1  // the noise convolution with eight outputs per thread from N = 2048 up (see response_pulse); 0: four everywhere
@@ -937,6 +948,11 @@ __device__ __forceinline__ void mp_fft(wh::ckp<double2> zb, wh::ckp<const double
 }
 template <int N>
 constexpr bool resp_wave_fft() { return N == 1024; }
+// A pulse whose record says vuv == 0 is unvoiced whatever the aperiodicity rows hold (synthesis.py:69), and an unvoiced
+// pulse's aperiodic spectrum is the spectrogram's: at the 16 kHz shape such a pulse does not fetch the two aperiodicity
+// rows.  The other lengths keep the code they had (they were not measured with it).
+template <int N>
+constexpr bool resp_skip_ap() { return WH_RESP_SKIP_AP && resp_wave_fft<N>(); }
 struct SpectrumIdentity {
   __device__ __forceinline__ double2 operator()(int, double2 e) const { return e; }
 };
@@ -1132,6 +1148,66 @@ __device__ __forceinline__ void ring_flush(wh::ckp<double> ring, int64_t a, int6
   }
 }
 
+// response_pulse's noise convolution of R <= 4 outputs per thread (the shift-free form described there) for response_pair:
+// acc[q] += sum_{j < cnt} nzb[j] * ra[mb0 + q - j], mb0 = m0 - j0, ra the padded response (rap_index), nzb the zero-mean noise,
+// zero-padded to a multiple of 2R.  The same loads and the same FMAs in the same order: the same bits.
+template <int R>
+__device__ __forceinline__ void noise_conv_groups(wh::ckp<double> rap, wh::ckp<double> nzb, int cnt, int m0, int64_t j0, double (&acc)[R]) {
+#if WH_SYN_CONTRACT
+#pragma clang fp contract(fast)
+#endif
+  auto load_group = [&](int base, double (&g)[R]) {  // base is a multiple of R: a group is all-valid or all before the start
+#pragma unroll
+    for (int t = 0; t < R; t += 2) {
+      double2 v = make_double2(0.0, 0.0);
+      if (base >= 0) v = wh::ck_as<const double2>(rap + rap_index(base + t))[0];
+      g[t] = v.x;
+      g[t + 1] = v.y;
+    }
+  };
+  auto block = [&](int j, const double (&hi)[R], const double (&lo)[R]) {
+    double n[R];
+#pragma unroll
+    for (int t = 0; t < R; t += 2) {
+      const double2 v = wh::ck_as<const double2>(nzb + (j + t))[0];
+      n[t] = v.x;
+      n[t + 1] = v.y;
+    }
+#pragma unroll
+    for (int sft = 0; sft < R; ++sft)
+#pragma unroll
+      for (int q = 0; q < R; ++q) acc[q] = fma(n[sft], q - sft >= 0 ? hi[q - sft] : lo[R + q - sft], acc[q]);
+  };
+  double ga[R], gb[R];
+  const int mb0 = m0 - (int)j0;
+  load_group(mb0, ga);
+  load_group(mb0 - R, gb);
+  const int steps = ((cnt + 2 * R - 1) / (2 * R)) * (2 * R);  // the noise is zero-padded up to a multiple of 2R
+  for (int j = 0; j < steps; j += 2 * R) {
+    block(j, ga, gb);
+    load_group(mb0 - j - 2 * R, ga);
+    block(j + R, gb, ga);
+    load_group(mb0 - j - 3 * R, gb);
+  }
+}
+
+// The ring's window moves on to the pulse whose first tap is s1: what it leaves behind goes to the row.
+template <int N>
+__device__ __forceinline__ void ring_advance(wh::ckp<double> ring, RunState& rs, wh::ckp<double> WH_RESTRICT row, int64_t s1, int64_t ny) {
+  constexpr int FT = ft_syn(N);
+  if (rs.any) {
+    const int64_t e = s1 < rs.win_start + N ? s1 : rs.win_start + N;  // the samples the window leaves behind
+    ring_flush<N>(ring, rs.win_start, e, row, rs.row_start, ny);
+    // (pulses more than N samples apart — f0 below fs / N: the samples between the two windows belong to the row too)
+    for (int64_t tgt = rs.win_start + N + WH_TID; tgt < (s1 < ny ? s1 : ny); tgt += FT) row[1 + (tgt - rs.row_start)] = 0.0;
+    wh::sync<FT>();
+  } else {
+    rs.row_start = s1 < 1 ? 1 : s1;
+  }
+  rs.any = true;
+  rs.win_start = s1;
+}
+
 // One pulse of a run.
 template <int N>
 __device__ __forceinline__ void response_pulse(const RespArgs& A, const PulseRec& rec, char* smem, wh::ckp<double> ring, RunState& rs,
@@ -1191,18 +1267,40 @@ __device__ __forceinline__ void response_pulse(const RespArgs& A, const PulseRec
   // across it), one global round trip per pulse instead of one per bin
   constexpr int KQ = (K + FT - 1) / FT;
   double rsl[KQ], rsh[KQ], ral[KQ], rah[KQ];
+  const bool need_ap = rec.vuv != 0;  // (workgroup-uniform, known from the record)
 #pragma unroll
   for (int q = 0; q < KQ; ++q) {
     const int k = WH_TID + q * FT;
     const int kc = k < K ? k : K - 1;  // (clamped: always a valid address; the surplus slot is not used)
     rsl[q] = s_lo[kc];
     rsh[q] = s_hi[kc];
-    ral[q] = a_lo[kc];
-    rah[q] = a_hi[kc];
+    if constexpr (resp_skip_ap<N>()) {
+      ral[q] = rah[q] = 0.0;
+    } else {
+      ral[q] = a_lo[kc];
+      rah[q] = a_hi[kc];
+    }
   }
   // aperiodic_slice[0] decides voicing (synthesis.py:69); its two loads ride with the rows' (issued first, they put
   // two more dependent round trips in front of the rows: the compiler waited for each before going on)
-  double ap0_lo = a_lo[0], ap0_hi = a_hi[0];
+  double ap0_lo, ap0_hi;
+  if constexpr (resp_skip_ap<N>()) {
+    ap0_lo = ap0_hi = 0.0;
+    if (need_ap) {
+#pragma unroll
+      for (int q = 0; q < KQ; ++q) {
+        const int k = WH_TID + q * FT;
+        const int kc = k < K ? k : K - 1;
+        ral[q] = a_lo[kc];
+        rah[q] = a_hi[kc];
+      }
+      ap0_lo = a_lo[0];
+      ap0_hi = a_hi[0];
+    }
+  } else {
+    ap0_lo = a_lo[0];
+    ap0_hi = a_hi[0];
+  }
   asm volatile("" : "+v"(ap0_lo), "+v"(ap0_hi));  // (both issued here: else the second is sunk behind the test of `same`)
   double aper0;
   {
@@ -1210,19 +1308,34 @@ __device__ __forceinline__ void response_pulse(const RespArgs& A, const PulseRec
     aper0 = same ? al : a * al + b * ah;
   }
   const bool voiced = (rec.vuv != 0) && (aper0 <= 0.999);
+  RSTAGE_COUNT(voiced ? 8 : (rec.vuv == 0 ? 9 : 10))
+  RSTAGE_COUNT(13)
 #pragma unroll
   for (int q = 0; q < KQ; ++q) {
     const int k = WH_TID + q * FT;
     if (k >= K) break;
     const double sl = rsl[q], sh = rsh[q];
-    const double al = ral[q] * ral[q], ah = rah[q] * rah[q];
-    const double pl = fmax(0.001, 1 - al), ph = fmax(0.001, 1 - ah);
-    const double sp = same ? sl : a * sl + b * sh;
-    const double pe = same ? pl : a * pl + b * ph;
-    const double ap = same ? al : a * al + b * ah;
-    double v = sp * pe;  // periodic spectrum
-    if (v == 0.0) v = 2.220446049250313e-16;
-    double w = voiced ? sp * ap : sp;  // aperiodic spectrum
+    double v, w;
+    auto spectra = [&]() {
+      double al = ral[q] * ral[q], ah = rah[q] * rah[q];
+      // (behind the voiced test the compiler fuses each square into its 1 - x, one rounding less than the reference's
+      // aperiodicity ** 2 and than this code took before the test: the squares stay values of their own)
+      if constexpr (resp_skip_ap<N>()) asm volatile("" : "+v"(al), "+v"(ah));
+      const double pl = fmax(0.001, 1 - al), ph = fmax(0.001, 1 - ah);
+      const double sp = same ? sl : a * sl + b * sh;
+      const double pe = same ? pl : a * pl + b * ph;
+      const double ap = same ? al : a * al + b * ah;
+      v = sp * pe;  // periodic spectrum
+      if (v == 0.0) v = 2.220446049250313e-16;
+      w = voiced ? sp * ap : sp;  // aperiodic spectrum
+    };
+    if constexpr (resp_skip_ap<N>()) {  // (an unvoiced pulse uses neither product: at the 16 kHz shape it skips the squares too)
+      v = 0.0;
+      w = same ? sl : a * sl + b * sh;
+      if (voiced) spectra();
+    } else {
+      spectra();
+    }
     if (w == 0.0) w = 2.220446049250313e-16;
     // log|.| / 2 of the Hermitian-mirrored spectrum (synthesis.py:103-105), written where the chain's first
     // transform reads it: no amplitude arrays, no separate log and mirror passes
@@ -1348,7 +1461,7 @@ __device__ __forceinline__ void response_pulse(const RespArgs& A, const PulseRec
     min_phase_response<N, FT, resp_wave_fft<N>()>(zbA, tw_base, 0.0);
     if (voiced) min_phase_response<N, FT, resp_wave_fft<N>()>(zbP, tw_base, coef_pi * shift);
   }
-  RSTAGE_MARK(2)
+  RSTAGE_MARK(voiced ? 2 : 6)
   if (side_noise) {
     // the mean of the run in block_sum's order: the wave sums the side waves left (visible behind the chains' last
     // barrier), added in wave order.  (A wave whose threads are all behind the run's last block adds 0.0 there: skipped.)
@@ -1443,6 +1556,7 @@ __device__ __forceinline__ void response_pulse(const RespArgs& A, const PulseRec
       // mb = m0 - j0 - j.  A block of R noise samples needs exactly these two groups (output q at step s reads
       // ra[mb + q - s]); for the next block lo becomes hi and ONE new group is fetched — into the registers of the group
       // that just died, so nothing is ever shifted (the two-step version moved 2(R-1) doubles per pair of steps).
+      // (response_pair runs the same form from noise_conv_groups; moving this copy there reschedules response_kernel<512>)
       auto load_group = [&](int base, double (&g)[R]) {  // base is a multiple of R: a group is all-valid or all before the start
   #pragma unroll
         for (int t = 0; t < R; t += 2) {
@@ -1533,17 +1647,7 @@ __device__ __forceinline__ void response_pulse(const RespArgs& A, const PulseRec
 
   // ---- overlap-add with the reference's clipped fancy-index semantics (Q8), through the run's ring ----------
   const int64_t s1 = pidx - N / 2 + 1;  // 1-based index of this pulse's first tap
-  if (rs.any) {
-    const int64_t e = s1 < rs.win_start + N ? s1 : rs.win_start + N;  // the samples the window leaves behind
-    ring_flush<N>(ring, rs.win_start, e, row, rs.row_start, m.ny);
-    // (pulses more than N samples apart — f0 below fs / N: the samples between the two windows belong to the row too)
-    for (int64_t tgt = rs.win_start + N + WH_TID; tgt < (s1 < m.ny ? s1 : m.ny); tgt += FT) row[1 + (tgt - rs.row_start)] = 0.0;
-    wh::sync<FT>();
-  } else {
-    rs.row_start = s1 < 1 ? 1 : s1;
-  }
-  rs.any = true;
-  rs.win_start = s1;
+  ring_advance<N>(ring, rs, row, s1, m.ny);
 #pragma unroll
   for (int q = 0; q < R; ++q) {
     const int mm = m0 + q;
@@ -1555,6 +1659,197 @@ __device__ __forceinline__ void response_pulse(const RespArgs& A, const PulseRec
     if (tgt < m.ny) ring[(int)(tgt & (N - 1))] += v;    // this thread is the only writer of its R slots
     else if (mm == N - 1) rs.last += v;                 // last duplicate wins on the high side: the last sample's share
   }
+  RSTAGE_MARK(4)
+}
+
+// Whether two consecutive pulses of a run share the chains (response_pair): decided from their records alone, the same
+// for every thread of the workgroup.
+template <int N>
+constexpr bool resp_pairs() { return WH_RESP_PAIR && WH_RESP_ROLES && resp_wave_fft<N>() && ft_syn(N) == 256; }
+__device__ __forceinline__ bool resp_pairable(const RespArgs& A, int vuv0, int noise_size0, int vuv1, int noise_size1) {
+  const int nd0 = noise_size0 > 3 ? noise_size0 : 3, nd1 = noise_size1 > 3 ? noise_size1 : 3;
+  return vuv0 == 0 && vuv1 == 0 && A.noise == nullptr && nd0 + nd1 <= 256;
+}
+
+// Two consecutive UNVOICED pulses of a run (both records say vuv == 0, device-stream noise, both noise runs fit nz together)
+// through the machinery of one voiced pulse.  An unvoiced pulse has the aperiodic chain only: alone, one of the workgroup's
+// four waves transforms and the periodic chain's buffer lies idle — and the reference places unvoiced pulses every 2 ms, in
+// long runs.  Here r0's chain runs in zbA on thread group 0 and r1's in zbP on group 1, in lockstep like a voiced pulse's
+// two; waves 1 and 3 generate the two noise runs under the first transform.  Each chain is the plan it is alone (8-8-8 on
+// one wave, the same bins per expression), each run takes the Philox blocks and forms its mean in the order it does alone,
+// and the ring receives r0's taps, then r1's: the output has the bits of the one-by-one path.  The spectrogram rows are
+// fetched once where both pulses interpolate the same pair of frames (the usual case: pulses 2 ms apart, frames 5 ms),
+// the aperiodicity rows not at all.
+template <int N>
+__device__ __forceinline__ void response_pair(const RespArgs& A, const PulseRec& r0, const PulseRec& r1, char* smem, wh::ckp<double> ring,
+                                              RunState& rs, wh::ckp<double> WH_RESTRICT row) {
+#if WH_SYN_CONTRACT
+#pragma clang fp contract(fast)
+#endif
+  const double* __restrict__ spectrogram = A.spectrogram;
+  const double2* __restrict__ tw_raw = A.tw_base;
+  asm volatile("" : "+s"(tw_raw));  // per pulse: no twiddle address / value of one pulse survives into the next
+  const wh::ckp<const double2> tw_base = wh::ck_make(tw_raw, WH_TWIDDLE_ENTRIES, wh::WH_CK_TWIDDLE);
+  constexpr int FT = ft_syn(N);
+  constexpr int K = N / 2 + 1;
+  constexpr int NZ = 256;
+  constexpr int R = N / FT;
+  constexpr int GT = FT / 2;
+  static_assert(GT == 2 * WH_WAVE && R <= 4 && 2 * NZ <= N, "one side wave per chain; the staged noise fits the first chain's buffer");
+  // (the LDS layout of response_pulse)
+  const wh::ckp<double> lds_all = wh::ck_make(reinterpret_cast<double*>(smem), 2 * (N + 2) + (N + N / 16 + 2) + NZ + 32, wh::WH_CK_LDS_OTHER);
+  const wh::ckp<double> zrA = wh::ck_sub(lds_all, 0, N + 2, wh::WH_CK_LDS_MAIN);     // r0's chain
+  const wh::ckp<double2> zbA = wh::ck_as<double2>(zrA);
+  const wh::ckp<double> zrP = wh::ck_sub(lds_all, N + 2, N + 2, wh::WH_CK_LDS_AUX);  // r1's chain
+  const wh::ckp<double2> zbP = wh::ck_as<double2>(zrP);
+  const wh::ckp<double> rap = wh::ck_sub(lds_all, 2 * (N + 2), N + N / 16 + 2, wh::WH_CK_LDS_OTHER);
+  const wh::ckp<double> nz = wh::ck_sub(lds_all, 2 * (N + 2) + (N + N / 16 + 2), NZ, wh::WH_CK_LDS_OTHER);
+  const wh::ckp<double> scratch = wh::ck_sub(lds_all, 2 * (N + 2) + (N + N / 16 + 2) + NZ, 32, wh::WH_CK_LDS_SCRATCH);
+
+  RSTAGE_BEGIN
+  wh::sync<FT>();
+  const int u = r0.u;
+  const int64_t ny = A.meta[u].ny;
+  RSTAGE_COUNT(9) RSTAGE_COUNT(9) RSTAGE_COUNT(12) RSTAGE_COUNT(13) RSTAGE_COUNT(13)
+  {  // ---- log spectra: the rows' registers die here, in front of the chains
+    const bool same_rows = r0.rows == r1.rows;  // (workgroup-uniform)
+    const double* s_lo0 = spectrogram + (r0.rows & 0xffffffffll) * K;
+    const double* s_hi0 = spectrogram + (r0.rows >> 32) * K;
+    const double* s_lo1 = spectrogram + (r1.rows & 0xffffffffll) * K;
+    const double* s_hi1 = spectrogram + (r1.rows >> 32) * K;
+    const bool same0 = r0.weight < 0.0, same1 = r1.weight < 0.0;
+    const double b0 = same0 ? 0.0 : r0.weight, b1 = same1 ? 0.0 : r1.weight;
+    const double a0 = 1 - b0, a1 = 1 - b1;
+    constexpr int KQ = (K + FT - 1) / FT;
+    double rl0[KQ], rh0[KQ], rl1[KQ], rh1[KQ];
+#pragma unroll
+    for (int q = 0; q < KQ; ++q) {
+      const int k = WH_TID + q * FT;
+      const int kc = k < K ? k : K - 1;  // (clamped: always a valid address; the surplus slot is not used)
+      rl0[q] = s_lo0[kc];
+      rh0[q] = s_hi0[kc];
+    }
+    if (same_rows) {
+#pragma unroll
+      for (int q = 0; q < KQ; ++q) {
+        rl1[q] = rl0[q];
+        rh1[q] = rh0[q];
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < KQ; ++q) {
+        const int k = WH_TID + q * FT;
+        const int kc = k < K ? k : K - 1;
+        rl1[q] = s_lo1[kc];
+        rh1[q] = s_hi1[kc];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < KQ; ++q) {
+      const int k = WH_TID + q * FT;
+      if (k >= K) break;
+      // an unvoiced pulse's aperiodic spectrum is the spectrogram's.  response_pulse's `a * sl + b * sh` is contracted to
+      // fma(a, sl, b * sh); written as a sum here, the second pulse's came out as fma(b, sh, a * sl) — an ulp apart in a few
+      // bins (1e-16 in the output) — so the form is spelled out
+      double w0 = same0 ? rl0[q] : fma(a0, rl0[q], b0 * rh0[q]);
+      double w1 = same1 ? rl1[q] : fma(a1, rl1[q], b1 * rh1[q]);
+      if (w0 == 0.0) w0 = 2.220446049250313e-16;
+      if (w1 == 0.0) w1 = 2.220446049250313e-16;
+      const double2 lg = log_pair_call(fabs(w0), fabs(w1));  // (the two pulses' logarithms like a voiced pulse's two)
+      const double l0 = lg.x / 2, l1 = lg.y / 2;
+      zrA[k] = l0;
+      zrP[k] = l1;
+      if (k > 0 && k < N / 2) {
+        zrA[N - k] = l0;
+        zrP[N - k] = l1;
+      }
+    }
+  }
+  RSTAGE_MARK(5)
+  // ---- the two noise runs: r0's on wave 1 into nz[0, nd0), r1's on wave 3 into nz[nd0, nd0 + nd1); wave sums of the 64-block
+  //      chunks in scratch[c / 64] and scratch[4 + c / 64] (response_pulse's noise_side: the same blocks, lanes and sums)
+  const int nd0 = r0.noise_size > 3 ? r0.noise_size : 3, nd1 = r1.noise_size > 3 ? r1.noise_size : 3;  // nd0 + nd1 <= NZ
+  const int64_t noff0 = r0.noff, noff1 = r1.noff;
+  const uint64_t seed = A.seed;
+  auto noise_side = [&](int i, int) {
+    const uint64_t key = philox_key(seed, (uint64_t)u);
+    const int lane = i & 63;
+    const int p = __builtin_amdgcn_readfirstlane(i - lane) >> 6;  // the chain this side wave belongs to
+    const int64_t noff = p == 0 ? noff0 : noff1;
+    const int nd = p == 0 ? nd0 : nd1, at = p == 0 ? 0 : nd0;
+    const int64_t blk0 = noff >> 1, b1 = (noff + nd - 1) >> 1;
+    for (int c = 0; blk0 + c <= b1; c += 64) {
+      const int64_t blk = blk0 + c + lane;
+      double part = 0.0;
+      if (blk <= b1) {
+        const double2 z = normal_pair(key, (uint64_t)blk);
+        const int j = (int)(2 * blk - noff);  // -1 .. nd-1
+        if (j >= 0) {
+          part += z.x;
+          nz[at + j] = z.x;
+        }
+        if (j + 1 < nd) {
+          part += z.y;
+          nz[at + j + 1] = z.y;
+        }
+      }
+      part = wh::wave_sum(part);
+      if (lane == 0) scratch[4 * p + (c >> 6)] = part;
+    }
+  };
+  wh::sync<FT>();  // the log spectra are visible
+  RSTAGE_MARK(0)
+  {
+    const int g = WH_TID / GT;
+    min_phase_response<N, GT, true>(g == 0 ? zbA : zbP, tw_base, 0.0, SpectrumIdentity(), noise_side);
+  }
+  RSTAGE_MARK(7)
+  // the means, each from its run's wave sums in wave order (response_pulse behind the chains)
+  double mean0, mean1;
+  {
+    const int nb0 = (int)(((noff0 + nd0 - 1) >> 1) - (noff0 >> 1)) + 1, nb1 = (int)(((noff1 + nd1 - 1) >> 1) - (noff1 >> 1)) + 1;
+    double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+    for (int w = 0; w < (NZ / 2 + 1 + 63) / 64; ++w) {
+      if (w * 64 < nb0) t0 += scratch[w];
+      if (w * 64 < nb1) t1 += scratch[4 + w];
+    }
+    mean0 = t0 / (double)nd0;
+    mean1 = t1 / (double)nd1;
+  }
+  // zrA[n] = N * r0's response, zrP[n] = N * r1's (both before fftshift).  r0's goes to the padded buffer; zrA is free then
+  // and takes both zero-mean runs, each zero-padded to NZ: r0's at zrA[0, NZ), r1's at zrA[NZ, 2 NZ)
+  for (int n = WH_TID; n < N; n += FT) rap[rap_index(n)] = zrA[(n + N / 2) & (N - 1)] / N;
+  wh::sync<FT>();
+  for (int j = WH_TID; j < NZ; j += FT) {
+    zrA[j] = j < nd0 ? nz[j] - mean0 : 0.0;
+    zrA[NZ + j] = j < nd1 ? nz[nd0 + j] - mean1 : 0.0;
+  }
+  wh::sync<FT>();
+  const int m0 = WH_TID * R;
+  // convolution and overlap-add, r0 then r1: the ring sees the additions in the order of the one-by-one path
+  auto excite_and_add = [&](wh::ckp<double> nzb, int nd, int64_t pidx) {
+    double acc[R];
+#pragma unroll
+    for (int q = 0; q < R; ++q) acc[q] = 0.0;
+    noise_conv_groups<R>(rap, nzb, nd, m0, 0, acc);
+    const int64_t s1 = pidx - N / 2 + 1;  // 1-based index of this pulse's first tap
+    ring_advance<N>(ring, rs, row, s1, ny);
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      const int mm = m0 + q;
+      const int64_t tgt = s1 + mm;
+      if (tgt < 1) continue;                                   // clipped to 1 and overwritten by the in-range tap
+      if (tgt < ny) ring[(int)(tgt & (N - 1))] += acc[q];      // this thread is the only writer of its R slots
+      else if (mm == N - 1) rs.last += acc[q];                 // last duplicate wins on the high side: the last sample's share
+    }
+  };
+  excite_and_add(zrA, nd0, r0.pidx);
+  RSTAGE_MARK(3)
+  wh::sync<FT>();  // every thread is done with r0's response; its taps are in the ring
+  for (int n = WH_TID; n < N; n += FT) rap[rap_index(n)] = zrP[(n + N / 2) & (N - 1)] / N;
+  wh::sync<FT>();
+  excite_and_add(zrA + NZ, nd1, r1.pidx);
   RSTAGE_MARK(4)
 }
 
@@ -1691,12 +1986,45 @@ __global__ __launch_bounds__(ft_syn(N), 4) void response_kernel(RespArgs A) {
     row_start = row_start < 1 ? 1 : row_start;
   }
   (void)row_start;
+  if constexpr (resp_pairs<N>()) {
+    // Two records travel: the pulse's own and its successor's, whose vuv and noise_size decide — with the pulse's — whether
+    // the two go through the chains together (response_pair).  A pair fetches the records two and three pulses ahead, a
+    // single pulse the one two ahead: every record is still read out a pulse or more after its load was issued.
+    uint32_t nxt_w = fetch_rec(gp0 + 1 < gp1 ? gp0 + 1 : gp0);
 #pragma unroll 1
-  for (int64_t gp = gp0; gp < gp1; ++gp) {
-    const PulseRec cur = unpack_rec(cur_w);
-    const uint32_t nxt_w = fetch_rec(gp + 1 < gp1 ? gp + 1 : gp);  // in flight under this whole pulse
-    response_pulse<N>(A, cur, smem, ring, rs, row, dcw);
-    cur_w = nxt_w;
+    for (int64_t gp = gp0; gp < gp1;) {
+      const PulseRec cur = unpack_rec(cur_w);
+      const int64_t last = gp1 - 1;
+      bool pair = false;
+      if (gp + 1 < gp1)
+        pair = resp_pairable(A, cur.vuv, cur.noise_size, __builtin_amdgcn_readlane((int)nxt_w, 12), __builtin_amdgcn_readlane((int)nxt_w, 11));
+      if (pair) {
+        const PulseRec nxt = unpack_rec(nxt_w);
+        const uint32_t w2 = fetch_rec(gp + 2 < last ? gp + 2 : last), w3 = fetch_rec(gp + 3 < last ? gp + 3 : last);
+        response_pair<N>(A, cur, nxt, smem, ring, rs, row);
+        cur_w = w2;
+        nxt_w = w3;
+        gp += 2;
+      } else {
+        const uint32_t w2 = fetch_rec(gp + 2 < last ? gp + 2 : last);
+        response_pulse<N>(A, cur, smem, ring, rs, row, dcw);
+        cur_w = nxt_w;
+        nxt_w = w2;
+        gp += 1;
+      }
+    }
+  } else {
+#pragma unroll 1
+    for (int64_t gp = gp0; gp < gp1; ++gp) {
+      const PulseRec cur = unpack_rec(cur_w);
+      const uint32_t nxt_w = fetch_rec(gp + 1 < gp1 ? gp + 1 : gp);  // in flight under this whole pulse
+#ifdef WH_RESP_STAGE_TIMER
+      if (gp + 1 < gp1 && resp_pairable(A, cur.vuv, cur.noise_size, __builtin_amdgcn_readlane((int)nxt_w, 12), __builtin_amdgcn_readlane((int)nxt_w, 11)))
+        RSTAGE_COUNT(11)
+#endif
+      response_pulse<N>(A, cur, smem, ring, rs, row, dcw);
+      cur_w = nxt_w;
+    }
   }
   wh::sync<FT>();
   if (rs.any) ring_flush<N>(ring, rs.win_start, rs.win_start + N, row, rs.row_start, A.meta[u].ny);
@@ -2375,10 +2703,10 @@ extern "C" int wh_peak_normalise(wh_ctx* ctx, void* stream, double* y, const int
 }
 
 #ifdef WH_RESP_STAGE_TIMER
-extern "C" int wh_debug_resp_stages(unsigned long long* out8, int reset) {
-  (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_resp_stage), sizeof(unsigned long long) * 8);
+extern "C" int wh_debug_resp_stages(unsigned long long* out16, int reset) {
+  (void)hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_resp_stage), sizeof(unsigned long long) * 16);
   if (reset) {
-    unsigned long long z[8] = {0};
+    unsigned long long z[16] = {0};
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_resp_stage), z, sizeof(z));
   }
   return 0;
