@@ -86,6 +86,21 @@ int wh_math_probe(wh_ctx* ctx, void* stream, int which, const double* in, double
  * transforms of n = 512 points, interleaved (re, im) doubles, in -> out; inverse = 1: exp(+2 pi i k j / n), not divided by
  * n.  (gt, snt): threads per transform group and per workgroup, one of (64, 64), (128, 256), (256, 256). */
 int wh_fft_probe(wh_ctx* ctx, void* stream, int n, int gt, int snt, int inverse, const double* in, double* out, int64_t count);
+/* Test hook: the workgroup-wide transforms of csrc/wh_device.h on DEVICE data, at the shapes the kernels instantiate them
+ * with (csrc/wh_fft_probe.hip lists them; any other shape fails with a message).  kind 0: fft_lds<n, inverse, nt, snt, maxr>,
+ * n complex -> n complex; 1: fft_lds_from_regs<n, false, nt, maxr>, the same, the input read straight into the registers of
+ * the first pass (x[q] = element tid + q nt); 2: rfft_lds<n, nt, snt, maxr>, n reals -> n / 2 + 1 complex; 3:
+ * irfft_lds<n, nt, snt, maxr>, n / 2 + 1 complex -> n reals; 4: fft_lds_wave<n, inverse, nt, snt>, n complex -> n complex on
+ * the first wave of each nt-thread group.  Complex values are interleaved (re, im) doubles, `count`
+ * transforms lie back to back in `in` and `out`; nothing is normalised.  A workgroup has snt threads and snt / nt buffers,
+ * one transform per nt-thread group, all advancing through the same barriers; the buffers of a half-filled last workgroup
+ * are zero.  inverse: 0 or 1 for kinds 0 and 4, 0 for kinds 1 and 2, 1 for kind 3. */
+int wh_fft_engine_probe(wh_ctx* ctx, void* stream, int kind, int n, int nt, int snt, int maxr, int inverse, const double* in,
+                        double* out, int64_t count);
+/* Test hook: the context's twiddle block (csrc/wh_device.h: the tables exp(-2 pi i k / n) at [n, 2n), n = 2 ... 32768, and the
+ * FFT passes' [k][r] tables behind them) copied to HOST memory as (re, im) doubles.  h_out == NULL: returns the number of
+ * entries; otherwise n_entries must be that number, and 0 is returned on success. */
+int wh_twiddle_read(wh_ctx* ctx, double* h_out, int64_t n_entries);
 /* The same flags without a host wait, for callers that keep a pipeline of batches in flight:
  *   wh_flags_post — enqueue (one 16-lane kernel on `stream`) the publication of the flags raised by everything before
  *     it on the stream to a pinned host word per flag, and clear them on the device (discard != 0: clear them

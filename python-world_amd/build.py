@@ -33,6 +33,7 @@ TU_FLAGS = {
     "wh_d4c.hip": ["-ffp-contract=fast-honor-pragmas"],
     "wh_cheaptrick.hip": ["-ffp-contract=fast-honor-pragmas"],
     "wh_synthesis.hip": ["-DWH_SYN_CONTRACT=1"],
+    "wh_fft_probe.hip": ["-ffp-contract=fast-honor-pragmas"],  # (a test hook: the transforms as most of their callers compile them)
 }
 
 

@@ -50,6 +50,8 @@ SIGNATURES = {
     "wh_bounds_selftest": (_int, [_vp, _vp]),
     "wh_math_probe": (_int, [_vp, _vp, _int, _vp, _vp, ctypes.c_int64]),
     "wh_fft_probe": (_int, [_vp, _vp, _int, _int, _int, _int, _vp, _vp, ctypes.c_int64]),
+    "wh_fft_engine_probe": (_int, [_vp, _vp, _int, _int, _int, _int, _int, _int, _vp, _vp, ctypes.c_int64]),
+    "wh_twiddle_read": (_int, [_vp, _vp, ctypes.c_int64]),
     "wh_flags_post": (_int, [_vp, _vp, _int]),
     "wh_flags_poll": (_int, [_vp, ctypes.POINTER(ctypes.c_int32)]),
     "wh_dio": (_int, [_vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _int, _vp, _vp, _vp, _vp, _vp, _int,

@@ -126,6 +126,19 @@ def main():
     y, _ = wb.decode_device(enc, seed=1, check=False)
     out["cfg5_flags"] = wb.rt.take_flags()
     out["cfg5_record"] = list(_hip.bounds_last())
+    # ---- the transform probe: one launch each of a handful of shapes (kind, n, nt, snt, maxr, inverse) ------------------
+    probe = {}
+    for shape in ((2, 128, 64, 64, 8, 0), (0, 2048, 256, 512, 8, 0), (0, 8192, 512, 512, 8, 0), (1, 2048, 256, 256, 8, 0),
+                  (2, 1024, 64, 64, 8, 0), (3, 4096, 512, 512, 8, 1)):
+        kind, n = shape[0], shape[1]
+        d_in, d_out = {0: (2 * n, 2 * n), 1: (2 * n, 2 * n), 2: (n, n + 2), 3: (n + 2, n)}[kind]
+        x_d = rt.to_device(np.random.RandomState(n).standard_normal(37 * d_in))
+        y_d = rt.empty((37 * d_out,))
+        rc = rt.lib.wh_fft_engine_probe(rt.ctx, rt.stream(), *shape, rt.ptr(x_d), rt.ptr(y_d), 37)
+        fl = rt.take_flags()
+        probe["-".join(str(v) for v in shape)] = {"rc": rc, "flag": fl[_hip.FLAG_OOB], "record": list(_hip.bounds_last()),
+                                                  "finite": bool(np.all(np.isfinite(y_d.cpu().numpy())))}
+    out["fft_probe"] = probe
     print("BOUNDS_JSON " + json.dumps(out))
 
 

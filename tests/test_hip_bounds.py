@@ -10,7 +10,8 @@ scan.  The test builds that variant (hipcc, ~1 min) if it is not there, runs tes
 expects: the positive control fires with the right record; the CheapTrick fixtures reproduce the reference with zero
 records; an f0 sweep from 1 Hz to 1.5 fs at five (rate, transform) pairs — caller-supplied contours the reference's
 estimators never return (world/cheaptrick.py:64-131 takes any f0) — stays inside every buffer; config 2 at its full
-size, a Harvest + Requiem batch and a 48 kHz utterance run clean."""
+size, a Harvest + Requiem batch and a 48 kHz utterance run clean; the transform probe (csrc/wh_fft_probe.hip), one launch
+each of a handful of shapes, stays inside its LDS buffers and the twiddle block."""
 import json
 import os
 import subprocess
@@ -22,7 +23,7 @@ pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-BOUNDS_TUS = ("wh_api", "wh_cheaptrick", "wh_stonemask", "wh_harvest", "wh_synthesis", "wh_d4c")
+BOUNDS_TUS = ("wh_api", "wh_cheaptrick", "wh_stonemask", "wh_harvest", "wh_synthesis", "wh_d4c", "wh_fft_probe")
 VARIANT = os.path.join(ROOT, "python-world_amd", "lib", "variants", "libworld_hip_bounds.so")
 
 
@@ -81,6 +82,14 @@ def test_off_regime_signals_run_clean(report):
 def test_whole_pipelines_run_clean(report):
     for key in ("config2", "harvest", "cfg5"):
         assert report[key + "_flags"] == [0] * 16, (key, report[key + "_flags"], report[key + "_record"])
+
+
+def test_transform_probe_stays_inside_its_buffers(report):
+    # 64 points on one wave, two chains in lockstep, the 128 KB transform, the register-fed first pass, rfft_lds on 64 threads,
+    # irfft_lds; 37 transforms each (a half-filled last workgroup where two share one)
+    assert len(report["fft_probe"]) == 6
+    for shape, r in report["fft_probe"].items():
+        assert r["rc"] == 0 and r["flag"] == 0 and r["record"] == [0, 0, 0, 0] and r["finite"], (shape, r)
 
 
 def test_shipped_library_is_not_a_bounds_build():
