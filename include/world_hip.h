@@ -393,6 +393,34 @@ int wh_warp_spectrum(wh_ctx* ctx, void* stream, double* spectrogram, int64_t n_f
 int wh_modify_duration(wh_ctx* ctx, void* stream, const wh_batch* b, const double* tp_in, double* tp_out,
                        const double* h_xp, const double* h_fp, int n_anchor);
 
+/* ---- Pitch from outside and another frame grid: what World.set_pitch leaves open  (world/main.py:164-168) ----------- */
+/* The reference's set_pitch raises NotImplementedError with the note that the values have to be resampled onto the frame
+ * times the spectrogram shares.  These two entries do that resampling with np.interp's own arithmetic, bit for bit:
+ * j = last knot with xp[j] <= x; fp[j] itself on an exact hit, at the last knot and beyond either end (the end values);
+ * otherwise slope = (fp[j+1]-fp[j]) / (xp[j+1]-xp[j]) and slope*(x-xp[j]) + fp[j], unfused — and, as NumPy does, where
+ * that is NaN slope*(x-xp[j+1]) + fp[j+1], and fp[j] where that is NaN too and fp[j] == fp[j+1].
+ *
+ * interp_contour: out[f] = np.interp(tp[f], time_u, value_u) for the utterance u of frame f.  The knot lists are ragged:
+ * utterance u owns h_time / h_value[h_knot_off[u] .. h_knot_off[u+1]) (HOST; h_knot_off[n_utt+1] starts at 0; every
+ * list holds at least one knot; times finite and strictly increasing, or the call fails before anything is launched).
+ * voiced_rule != 0 (WORLD contours hold 0 at unvoiced frames; a straight line from 0 Hz to 200 Hz is no pitch): a frame
+ * is voiced iff every knot np.interp reads for it — both bracketing ones, or the single one — has value > 0; voiced
+ * frames get the interpolated value and vuv_out = 1, all others out = 0 and vuv_out = 0.  vuv_out (DEVICE, may be NULL)
+ * is written in that mode only.  out must not alias tp. */
+int wh_interp_contour(wh_ctx* ctx, void* stream, const wh_batch* b, const double* tp, const int64_t* h_knot_off,
+                      const double* h_time, const double* h_value, int voiced_rule, double* out, double* vuv_out);
+/* regrid_rows: a frame-major tensor in[src frames][k_bins] moved to another frame grid,
+ * out[f'][k] = np.interp(tp_dst[f'], tp_src of u, in[frames of u][k]) for the utterance u of destination frame f' — `src`
+ * and `dst` describe the same utterances (frame offsets of the two grids), no row of another utterance is ever read.
+ * tp_src must be strictly increasing inside every utterance (the caller's check: it is device data); an utterance with
+ * destination frames needs at least one source frame.  k_bins >= 1: spectrogram and aperiodicity rows, band rows, and
+ * with k_bins = 1 per-frame scalars.  positive_rule != 0: the rule of wh_interp_contour per element — 0 unless every
+ * source value read is > 0 (f0, vuv and gates: a gate stays 1 only where every source frame read has it).  The search
+ * runs once per destination frame in a kernel of its own; the row kernel reads at most two source rows per output row.
+ * out must not overlap in. */
+int wh_regrid_rows(wh_ctx* ctx, void* stream, const wh_batch* src, const wh_batch* dst, const double* tp_src,
+                   const double* tp_dst, const double* in, double* out, int k_bins, int positive_rule);
+
 /* ---- 16-bit PCM at the batch boundary (the reference's WAV usage: example/prosody.py:12-13,57) ---------------------- */
 /* x[i] = pcm[i] / (2^15 - 1); pcm[i] = int16(trunc(y[i] * 2^15)) (low 16 bits, like NumPy's astype on the reference's
  * platform).  DEVICE pointers: the 2-byte samples cross PCIe instead of the 8-byte ones. */

@@ -248,6 +248,41 @@ class BatchEncoding:
         self.f0 *= factor
         return self
 
+    def set_pitch_contour(self, times, values=None, voiced_rule=True):
+        """A pitch contour from outside — a laryngograph track, another tracker's output, a hand-edited contour, another
+        speaker's prosody — interpolated onto this encoding's frame times on the device: what the reference's set_pitch
+        leaves open (world/main.py:164-168).  ``times`` / ``values``: one pair of 1-D arrays for every utterance, or a
+        list with one array per utterance on each side (``values=None``: a list of (time, value) pairs).  Every frame
+        gets np.interp(tp, time, value), bit for bit.  ``voiced_rule`` (default): a frame is voiced iff every knot
+        np.interp reads for it has value > 0; voiced frames get the interpolated value and vuv = 1, the others f0 = 0
+        and vuv = 0 — no glide from 0 Hz into a voiced stretch.  Off: plain interpolation, vuv = (f0 > 0).  Installs new
+        f0 / vuv tensors and drops a prefetched time base, as scale_pitch does.  ValueError (before anything reaches the
+        device) for a wrong number of lists, lengths that disagree and times that are not finite and strictly
+        increasing."""
+        from .regrid import interp_contour_device, knot_lists
+
+        off, t, v = knot_lists(times, values, self.n_utt, "set_pitch_contour")
+        rt = self.rt
+        with rt.lock, rt.on_stream():
+            f0, vuv = interp_contour_device(rt, self.batch, self._tp, off, t, v, voiced_rule)
+            if vuv is None:
+                vuv = (f0 > 0).to(f0.dtype)
+        self._timebase = None
+        self.f0, self.vuv = f0, vuv
+        return self
+
+    def regrid(self, frame_period):
+        """This encoding on the frame grid of ``frame_period`` ms, as a NEW BatchEncoding on a batch descriptor of its
+        own: per utterance the frame times arange(n') * frame_period / 1000 (shifted by its first frame time when that
+        is not 0) up to its last frame time, and every row np.interp of the source rows over the utterance's own frame
+        times, bit for bit (wh_regrid_rows) — spectrogram, aperiodicity, coarse_ap when present; f0, vuv and ap_gate by
+        the both-bracketing rule (0 unless every source value read is > 0).  Works from any source grid: the 5 ms
+        analysis grid, or the non-uniform times scale_duration / modify_duration leave.  An untouched encoding regridded
+        to its own period is returned bit for bit.  The result holds no 'ps spectrogram' and no prefetched time base;
+        compact(), decode_device, to_dicts and the feature heads take it as they take any encoding."""
+        from .regrid import regrid_encoding
+        return regrid_encoding(self, frame_period)
+
     def scale_duration(self, factor):
         """world/main.py:170-178, on the device."""
         self._timebase = None
@@ -475,6 +510,7 @@ class WorldBatch:
             tp_h = np.concatenate([_tables.frame_times(n, frame_period) for n in nfs])
         tp_d = rt.to_device(tp_h)
         batch.tp_d, batch.tp_host = tp_d, tp_h  # the frame grid belongs to the batch descriptor (no pointer-keyed lookup)
+        batch.frame_period = frame_period
         return batch, x_d, tp_d
 
     @_on_lane_stream
@@ -516,6 +552,42 @@ class WorldBatch:
             raise Exception
         if f0_done is not None:
             f0_done()
+        retry = None
+        if f0_method == 'harvest' and event_caps is None:
+            def retry():
+                # more crossings than estimated: everything behind Harvest worked on an unusable contour (whatever else
+                # it reported goes with it) — once more, with the capacities this pass counted
+                from .harvest import counted_event_caps
+                if self._tb_rt is not None:
+                    self._tb_rt.take_flags()
+                return self.encode_device(batch, x_d, tp_d, fs, f0_method, f0_floor, f0_ceil, channels_in_octave, target_fs,
+                                          frame_period, allowed_range, fft_size, is_requiem, None, True, want_ps,
+                                          counted_event_caps(rt), want_coarse)
+        return self._encode_from_f0(batch, x_d, tp_d, fs, f0_d, vuv_d, fft_size, is_requiem, check, want_ps, want_coarse,
+                                    frame_period, "encode_device", retry)
+
+    @_on_lane_stream
+    def encode_given_f0(self, batch, x_d, tp_d, fs, f0_d, vuv_d, fft_size=None, is_requiem=False, check=True,
+                        want_ps=False, want_coarse=False):
+        """encode_device under a contour the caller supplies (World.encode_w_gvn_f0, world/main.py:81-104, for a resident
+        batch): everything encode_device enqueues behind its F0 stage — the time-base prefetch, CheapTrick, D4C or
+        d4cRequiem, the gate — on ``f0_d`` / ``vuv_d`` [F], commonly wh_interp_contour's output on the batch's own
+        grid (world.regrid.interp_contour_device).  The two tensors are not modified: CheapTrick and D4C rewrite f0 in
+        place (500 Hz below the floor, 0 at unvoiced frames), on a copy that the result keeps.  ``check`` / ``want_ps`` /
+        ``want_coarse``: as in encode_device."""
+        self._deferred_begin(check, "encode_given_f0")
+        nf = batch.total_frames
+        if tuple(f0_d.shape) != (nf,) or tuple(vuv_d.shape) != (nf,):
+            raise ValueError("encode_given_f0: f0 and vuv must hold one value per frame (%d), got %s and %s"
+                             % (nf, tuple(f0_d.shape), tuple(vuv_d.shape)))
+        return self._encode_from_f0(batch, x_d, tp_d, fs, f0_d.clone(), vuv_d.clone(), fft_size, is_requiem, check, want_ps,
+                                    want_coarse, getattr(batch, "frame_period", None), "encode_given_f0", None)
+
+    def _encode_from_f0(self, batch, x_d, tp_d, fs, f0_d, vuv_d, fft_size, is_requiem, check, want_ps, want_coarse,
+                        frame_period, where, retry):
+        """What encode_device and encode_given_f0 share: everything behind the F0 stage.  ``retry``: what a checked call
+        does instead of raising when Harvest's crossing lists overflowed (None: nothing to repeat)."""
+        rt = self.rt
         ct_fft = int(fft_size) if fft_size is not None else default_fft_size(fs)
         tp_host = batch.tp_host if getattr(batch, "tp_d", None) is tp_d else None
         timebase = None
@@ -532,16 +604,9 @@ class WorldBatch:
             rt.post_flags()
         elif check:
             flags = rt.take_flags()
-            if flags[_hip.FLAG_EVENT_OVERFLOW] and f0_method == 'harvest' and event_caps is None:
-                # more crossings than estimated: everything behind Harvest worked on an unusable contour (whatever else
-                # it reported goes with it) — once more, with the capacities this pass counted
-                from .harvest import counted_event_caps
-                if self._tb_rt is not None:
-                    self._tb_rt.take_flags()
-                return self.encode_device(batch, x_d, tp_d, fs, f0_method, f0_floor, f0_ceil, channels_in_octave, target_fs,
-                                          frame_period, allowed_range, fft_size, is_requiem, None, True, want_ps,
-                                          counted_event_caps(rt), want_coarse)
-            rt.raise_for_flags(flags, "encode_device")
+            if flags[_hip.FLAG_EVENT_OVERFLOW] and retry is not None:
+                return retry()
+            rt.raise_for_flags(flags, where)
         enc = BatchEncoding(rt, batch, fs, tp_d.clone(), f0_d, vuv_d, spec_d, ap_d, ct_fft, is_requiem, frame_period,
                             tp_host=None if tp_host is None else tp_host.copy(), ps_spectrogram=ps_d)
         enc.coarse_ap, enc.ap_gate = coarse_d, gate_d
@@ -676,6 +741,7 @@ class WorldBatch:
         tp_h = np.concatenate([_tables.frame_times(n, frame_period) for n in nfs])
         tp_d = rt.to_device(tp_h)
         batch.tp_d, batch.tp_host = tp_d, tp_h
+        batch.frame_period = frame_period
         return batch, x_d, tp_d
 
     @_on_lane_stream
@@ -724,6 +790,7 @@ class WorldBatch:
             tp_h = np.concatenate([_tables.frame_times(n, frame_period) for n in nfs]) if nfs else np.zeros(0)
         tp_d = rt.to_device(tp_h)
         batch.tp_d, batch.tp_host = tp_d, tp_h
+        batch.frame_period = frame_period
         return batch, x_d, tp_d
 
     def encode_resampled(self, xs, fs_in, fs_out, **kw):

@@ -357,6 +357,68 @@ class World(object):
             _hand_out(dats[a:b], out, y_off2, copy_out)
         return dats
 
+    @_hip.serialised
+    def encode_batch_w_gvn_f0(self, fs, xs, sources, fft_size=None, is_requiem=False, devices=None):
+        """encode_w_gvn_f0 (world/main.py:81-104) for a list of utterances in one pass per kernel: ``sources[u]`` is the
+        dict with 'temporal_positions', 'f0' and 'vuv' that goes with ``xs[u]``.  A source whose temporal_positions are
+        the batch's own 5 ms grid is taken as it is; any other — a 10 ms tracker, a laryngograph's time stamps — is
+        interpolated onto the grid on the device with the voiced rule (BatchEncoding.set_pitch_contour).  Returns a list
+        of dicts with encode_w_gvn_f0's keys and that utterance's values, bit for bit; a Requiem dict has no
+        'coarse_ap' (the reference raises KeyError there: SURVEY Q16).  The reference's quirks stay: the assert on every
+        source's f0, TypeError for fft_size=None.  The sources are not modified."""
+        from .batch import WorldBatch
+        from .regrid import interp_contour_device, knot_lists
+
+        if devices is not None:
+            raise NotImplementedError("encode_batch_w_gvn_f0(devices=...): run one WorldBatch per device instead")
+        xs, sources = list(xs), list(sources)
+        if len(sources) != len(xs):
+            raise ValueError("encode_batch_w_gvn_f0: %d sources for %d utterances" % (len(sources), len(xs)))
+        for source in sources:
+            assert np.all(source['f0'] >= 3 * fs / fft_size)
+            _hip.same_frames("encode_batch_w_gvn_f0", temporal_positions=source['temporal_positions'], f0=source['f0'],
+                             vuv=source['vuv'])
+        if not xs:
+            return []
+        wb = WorldBatch()
+        rt = wb.rt
+        batch, x_d, tp_d = wb.upload(xs, fs)
+        fo = batch.frame_off
+        grid = [batch.tp_host[int(fo[u]):int(fo[u + 1])] for u in range(len(xs))]
+        as_is = [np.array_equal(np.asarray(s['temporal_positions'], dtype=np.float64), g) for s, g in zip(sources, grid)]
+        f64 = lambda a: np.asarray(a, dtype=np.float64)  # noqa: E731
+        with rt.lock, rt.on_stream():
+            if all(as_is):
+                scal = rt.to_device_concat([f64(s[k]) for k in ('f0', 'vuv') for s in sources]).view(2, -1)
+                f0_d, vuv_d = scal[0], scal[1]
+            else:
+                # (a source on the grid passes through the exact-hit rule value for value; its vuv is the caller's to
+                # say, so those utterances' slices are overwritten with what was passed)
+                off, t, v = knot_lists([s['temporal_positions'] for s in sources], [s['f0'] for s in sources], len(xs),
+                                       "encode_batch_w_gvn_f0")
+                f0_d, vuv_d = interp_contour_device(rt, batch, tp_d, off, t, v, True)
+                for u, s in enumerate(sources):
+                    if as_is[u]:
+                        f0_d[int(fo[u]):int(fo[u + 1])] = rt.to_device(f64(s['f0']))
+                        vuv_d[int(fo[u]):int(fo[u + 1])] = rt.to_device(f64(s['vuv']))
+        enc = wb.encode_given_f0(batch, x_d, tp_d, fs, f0_d, vuv_d, fft_size=fft_size, is_requiem=is_requiem,
+                                 want_coarse=not is_requiem)
+        dats = enc.to_dicts()
+        with rt.lock, rt.on_stream():
+            coarse = None if is_requiem else [rt.to_host(enc.coarse_ap[int(fo[u]):int(fo[u + 1])], transpose=True)
+                                              for u in range(len(xs))]
+        out = []
+        for u, d in enumerate(dats):
+            o = _pick(d, _SOURCE_KEYS)
+            o['fs'] = fs
+            o['spectrogram'] = d['spectrogram']
+            o['aperiodicity'] = d['aperiodicity']
+            if not is_requiem:
+                o['coarse_ap'] = coarse[u]
+            o['is_requiem'] = is_requiem
+            out.append(o)
+        return out
+
     # ---- compact encodings (not in the reference's class; world/compact.py) --------------------------------------
     @_hip.serialised
     def encode_compact_batch(self, fs, xs, n0=40, devices=None, **encode_kw):
@@ -419,6 +481,43 @@ class World(object):
 
     def set_pitch(self, dat, time, value):
         raise NotImplementedError  # world/main.py:164-165
+
+    @_hip.serialised
+    def set_pitch_contour(self, dat, time, value):
+        """What the reference's set_pitch describes and leaves unimplemented (world/main.py:164-168: the values "need to
+        [be] resample[d] ... at given temporal positions (which are presumably shared with the spectrogram)"): the contour
+        (time [s], value [Hz], 0 = unvoiced) interpolated onto dat['temporal_positions'] with np.interp's arithmetic on
+        the device (BatchEncoding.set_pitch_contour, voiced rule on: no glide between 0 Hz and a voiced knot).  Replaces
+        dat['f0'] and dat['vuv'], returns dat; reference dicts and encode_batch's lazy dicts alike.  set_pitch itself
+        stays the reference's NotImplementedError."""
+        from .regrid import interp_contour_device, knot_lists
+
+        tp = np.ascontiguousarray(dat['temporal_positions'], dtype=np.float64)
+        if tp.ndim != 1:
+            raise ValueError("set_pitch_contour: temporal_positions must be 1-D, got shape %s" % (tp.shape,))
+        off, t, v = knot_lists(time, value, 1, "set_pitch_contour")
+        rt = _hip.Runtime.get()
+        with rt.lock, rt.on_stream():
+            batch = rt.make_batch([0, 0], [0, len(tp)])
+            f0_d, vuv_d = interp_contour_device(rt, batch, rt.to_device(tp), off, t, v, True)
+            f0, vuv = rt.torch.stack([f0_d, vuv_d]).cpu().numpy()
+        dat['f0'], dat['vuv'] = f0.copy(), vuv.copy()
+        return dat
+
+    @_hip.serialised
+    def regrid(self, dat, frame_period):
+        """dat on the frame grid of ``frame_period`` ms (BatchEncoding.regrid for one dict): replaces temporal_positions,
+        f0, vuv, spectrogram and aperiodicity — every row np.interp over the dict's own frame times, bit for bit, f0 / vuv
+        by the both-bracketing rule — and returns dat.  Any source grid: another period, or the non-uniform times
+        scale_duration / modify_duration leave.  Other keys ('ps spectrogram', 'coarse_ap', 'out') are left as they are."""
+        from .batch import BatchEncoding, WorldBatch
+
+        _hip.same_frames("regrid", temporal_positions=dat['temporal_positions'], f0=dat['f0'], vuv=dat['vuv'])
+        wb = WorldBatch()
+        new = BatchEncoding.from_dicts(wb.rt, [dat]).regrid(frame_period).to_dicts()[0]
+        for key in ('temporal_positions', 'f0', 'vuv', 'spectrogram', 'aperiodicity'):
+            dat[key] = new[key]
+        return dat
 
     def scale_duration(self, dat, factor):
         """world/main.py:170-178."""
