@@ -5,16 +5,7 @@
 // Replaces cheaptrick()/estimate_one_slice() of the reference (world/cheaptrick.py:9-157).
 #include "wh_host.h"
 #include "wh_math.h"
-#ifndef WH_FAST_MATH64
-#define WH_FAST_MATH64 1  // wh_math.h's log / exp for the 2 x 513 transcendentals of a frame (0: the device library's)
-#endif
-#if WH_FAST_MATH64
-#define WH_CT_LOG wh::flog
-#define WH_CT_EXP exp
-#else
-#define WH_CT_LOG log
-#define WH_CT_EXP exp
-#endif
+// (the 2 x 513 transcendentals of a frame: wh_math.h's flog, the device library's exp)
 #include "wh_spectral.h"
 
 namespace {
@@ -180,7 +171,7 @@ __global__ __launch_bounds__(ft_ct(N), ct_minw(N)) void cheaptrick_kernel(
     // that guarantee (digital silence) deterministically
 #pragma unroll
     for (int r = 0; r < KR; ++r)
-      if (k0 + r < K) aux[k0 + r] = WH_CT_LOG(bandv[r] * scale_f0 + 0.5 * 2.220446049250313e-16);
+      if (k0 + r < K) aux[k0 + r] = wh::flog(bandv[r] * scale_f0 + 0.5 * 2.220446049250313e-16);
   }
   wh::sync<FT>();
 
@@ -222,11 +213,7 @@ __global__ __launch_bounds__(ft_ct(N), ct_minw(N)) void cheaptrick_kernel(
   // transform — one pass over the half spectrum instead of three (wh::rfft_lds / multiply / wh::irfft_lds).
   {
     constexpr int M = N / 2;
-#if defined(WH_CT_ABLATE_T) && WH_CT_ABLATE_T
-    wh::sync<FT>();  // TIMING EXPERIMENT ONLY (wrong results): one of the two lifter transforms costs nothing — the upper bound
-#else                // of halving both (real-even data: DCT-I through quarter-size transforms)
     wh::fft_lds<M, false, FT>(zb, tw + M);  // (its barriers also complete the lifter table for the loop below)
-#endif
     const wh::ckp<const double2> WH_RESTRICT wtw = tw + N;
     for (int k = threadIdx.x; k <= M / 2; k += FT) {
       const double2 a = zb[k], b = zb[M - k];
@@ -251,7 +238,7 @@ __global__ __launch_bounds__(ft_ct(N), ct_minw(N)) void cheaptrick_kernel(
     wh::fft_lds<M, true, FT>(zb, tw + M);
   }
   const wh::ckp<double> o = wh::ck_make(spec_out + f * (int64_t)K, K, wh::WH_CK_OUT);
-  for (int k = threadIdx.x; k < K; k += FT) o[k] = WH_CT_EXP(zr[k] * (1.0 / N));  // N is a power of two: exact
+  for (int k = threadIdx.x; k < K; k += FT) o[k] = exp(zr[k] * (1.0 / N));  // N is a power of two: exact
 }
 
 template <int N>

@@ -15,24 +15,10 @@
 // offsets and index-to-double conversions as common subexpressions of all of them, computes them once and parks them
 // in registers for the whole kernel (193 VGPRs wanted where four workgroups per CU allow 128).  Re-deriving them per
 // use costs a few integer instructions.
-// Round-6 experiment (tools/build_variants.py): WH_D4C_PAIR frames per workgroup, one after the other;
-// WH_D4C_HOIST=1 lifts the three fences (plain thread index, fresh_table, stage_fence) so that the compiler may keep the
-// per-thread addresses, twiddles and index conversions it wants in registers and share them across the frames of a
-// workgroup and all their transforms; WH_D4C_PAIR_MINW sets the register budget (2: 256 VGPRs).  Shipped: 1 / 0.
-#ifndef WH_D4C_PAIR
-#define WH_D4C_PAIR 1
-#endif
-#ifndef WH_D4C_HOIST
-#define WH_D4C_HOIST 0
-#endif
-#ifndef WH_D4C_PAIR_MINW
-#define WH_D4C_PAIR_MINW 2
-#endif
+// (Several frames per workgroup with the three fences lifted — this one, fresh_table, stage_fence — lost: DESIGN.md §4 round 6.)
 __device__ __forceinline__ int wh_opaque_tid() {
   int t = threadIdx.x;
-#if !WH_D4C_HOIST
   asm volatile("" : "+v"(t));
-#endif
   return t;
 }
 #define WH_TID wh_opaque_tid()
@@ -40,32 +26,19 @@ __device__ __forceinline__ int wh_opaque_tid() {
 #include "wh_spectral.h"
 #include "wh_apbands.h"
 
-#ifndef WH_D4C_ABLATE
-#define WH_D4C_ABLATE 0
-#endif
-// FFT radix caps of d4c_kernel by transform length.  At 128 VGPRs (four workgroups per CU) the radix-8 plan fits
-// N <= 1024 without spilling; at N = 2048 / 4096 it spills ~23 registers — still 2 % faster, but the spills are HBM
-// traffic (1.86 GB per launch where the kernel's compulsory bytes are 0.61 GB), so those lengths keep radix 4.
 #ifndef WH_D4C_KEEP_W
 #define WH_D4C_KEEP_W 4  // rows of a register-fed window whose window values survive from the first walk to the second
 #endif
-#ifndef WH_D4C_GATHER_UNCOND
-#define WH_D4C_GATHER_UNCOND 1
-#endif
-#ifndef WH_D4C_REGFED
-#define WH_D4C_REGFED 1  // windows keep their samples in registers and feed the first (radix-8) FFT pass directly
-#endif
+// FFT radix caps of d4c_kernel's complex and real transforms: radix 8 at every length (the register-fed windows feed a
+// radix-8 first pass).  -DWH_D4C_MAXR / -DWH_D4C_RMAXR = 4 or 8 force one (tools/build_variants.py).
 #ifndef WH_D4C_RMAXR
-#define WH_D4C_RMAXR 0  // 0: by length (below); 4 / 8: forced
+#define WH_D4C_RMAXR 0  // 0: radix 8; 4 / 8: forced
 #endif
 #ifndef WH_D4C_MAXR
 #define WH_D4C_MAXR 0
 #endif
-constexpr int d4c_maxr(int n) { return WH_D4C_MAXR ? WH_D4C_MAXR : ((n <= 1024 || WH_D4C_REGFED) ? 8 : 4); }
-constexpr int d4c_rmaxr(int n) { return WH_D4C_RMAXR ? WH_D4C_RMAXR : ((n <= 1024 || WH_D4C_REGFED) ? 8 : 4); }
-#ifndef WH_LOVE_REGWIN
-#define WH_LOVE_REGWIN 1
-#endif
+constexpr int d4c_maxr(int) { return WH_D4C_MAXR ? WH_D4C_MAXR : 8; }
+constexpr int d4c_rmaxr(int) { return WH_D4C_RMAXR ? WH_D4C_RMAXR : 8; }
 #ifndef WH_LOVE_MAXR
 #define WH_LOVE_MAXR 8
 #endif
@@ -74,9 +47,6 @@ constexpr int d4c_rmaxr(int n) { return WH_D4C_RMAXR ? WH_D4C_RMAXR : ((n <= 102
 #endif
 #ifndef WH_D4C_WIN_UNROLL
 #define WH_D4C_WIN_UNROLL 4
-#endif
-#ifndef WH_D4C_CENT_LOOP
-#define WH_D4C_CENT_LOOP 0
 #endif
 // -DWH_D4C_STAGE_TIMER: thread 0 of every workgroup adds the shader-clock cycles between stage boundaries to
 // g_d4c_stage[] (read with wh_debug_d4c_stages, tools/d4c_stage_timer.py) — the per-stage latencies quoted in DESIGN.md.
@@ -97,16 +67,12 @@ namespace {
 // (203 VGPRs); passing the table pointer through an empty asm before each transform makes every instance re-derive
 // what it needs from L1/L2-resident data.
 __device__ __forceinline__ const double2* fresh_table(const double2* p) {
-#if !WH_D4C_HOIST
   asm volatile("" : "+s"(p));
-#endif
   return p;
 }
 #if WH_BOUNDS
 __device__ __forceinline__ wh::ckp<const double2> fresh_table(wh::ckp<const double2> p) {
-#if !WH_D4C_HOIST
   asm volatile("" : "+s"(p.p));
-#endif
   return p;
 }
 #endif
@@ -115,9 +81,7 @@ __device__ __forceinline__ wh::ckp<const double2> fresh_table(wh::ckp<const doub
 // stage's loads and transcendental set-up underneath the current stage's transform (which it does otherwise, and
 // pays for with ~60 VGPRs of values parked across the FFT).
 __device__ __forceinline__ double stage_fence(double v) {
-#if !WH_D4C_HOIST
   asm volatile("" : "+v"(v));
-#endif
   return v;
 }
 
@@ -128,7 +92,7 @@ __device__ __forceinline__ double stage_fence(double v) {
 // leave one workgroup per CU and the thread count is the only occupancy there is.
 // At N = 1024 (D4C-Requiem at 16 kHz) 128 threads make N = 8 * FT, the shape of the register-fed windows.
 #ifndef WH_FT_D4C_1024
-#define WH_FT_D4C_1024 (WH_D4C_REGFED ? WH_FT_D4C / 2 : WH_FT_D4C)
+#define WH_FT_D4C_1024 (WH_FT_D4C / 2)
 #endif
 #ifndef WH_FT_D4C_4096
 #define WH_FT_D4C_4096 (2 * WH_FT_D4C)  // (1024 threads, staged windows: 62.9 ms at config 5 — 50.8 compiled for 8 waves
@@ -143,9 +107,9 @@ constexpr int ft_of(int n) { return n >= 8192 ? 2 * WH_FT_D4C : n >= 4096 ? WH_F
 #define WH_D4C_MINBLK4096 4
 #endif
 #ifndef WH_D4C_MINBLK1024
-// N <= 1024 (D4C-Requiem at 16 kHz).  Staged form: 96 VGPRs, five 4-wave workgroups per CU (17 KB of LDS each).  Register-
-// fed form (two waves per frame): the radix-8 butterflies need the 128-register budget; eight workgroups per CU.
-#define WH_D4C_MINBLK1024 (WH_D4C_REGFED ? 4 : 5)
+// N = 1024 (D4C-Requiem at 16 kHz), register-fed, two waves per frame: the radix-8 butterflies need the 128-register
+// budget; eight workgroups per CU.
+#define WH_D4C_MINBLK1024 4
 #endif
 // (N = 8192, 96 kHz material: 131 KB of LDS per frame -> one 512-thread workgroup per CU, 256 registers per thread)
 constexpr int minblk_of(int n) { return n >= 8192 ? 1 : n >= 4096 ? WH_D4C_MINBLK4096 : (n == 1024 ? WH_D4C_MINBLK1024 : (n < 1024 ? 5 : WH_D4C_MINBLK)); }
@@ -355,18 +319,10 @@ __device__ __forceinline__ void d4c_window_regs(wh::ckp<const double> WH_RESTRIC
   // last sample, one line for the whole wave) and the rows past nq zeroed by a select.  Written as `if (q < nq) out[q] =
   // sample(..)` the compiler made a chain of conditional blocks, each WAITING for its load before the next block's and
   // copying the whole array between them: nq dependent global round trips and ~25 register moves per row.
-#if WH_D4C_GATHER_UNCOND
 #pragma unroll
   for (int q = 0; q < Q; ++q) out[q] = sample(threadIdx.x + q * FT);
 #pragma unroll
   for (int q = 0; q < Q; ++q) out[q] = q < nq ? out[q] : 0.0;
-#else
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    out[q] = 0.0;
-    if (q < nq) out[q] = sample(threadIdx.x + q * FT);
-  }
-#endif
   const double rot_s = ws.rot_s, rot_c = ws.rot_c;
   const double c0 = ws.base_c * e_tid.y - ws.base_s * e_tid.x;  // phase of this thread's first sample: base * E[tid]
   const double s0 = ws.base_s * e_tid.y + ws.base_c * e_tid.x;
@@ -471,7 +427,7 @@ inline D4cLaunchConst d4c_launch_const(double fs, int n, int wlen, int interval,
 }
 
 template <int N>
-constexpr bool d4c_regfed() { return WH_D4C_REGFED && N == 8 * ft_of(N); }
+constexpr bool d4c_regfed() { return N == 8 * ft_of(N); }
 
 // Threads per frame of the stand-alone gate kernel: its one transform is real (N/2 complex points), so N/16 threads are
 // one radix-8 butterfly each — half of d4c_kernel's count.
@@ -508,7 +464,6 @@ __global__ __launch_bounds__(ft_love(NLT)) void love_train_kernel(
   const double cf = fmax(f0, 40.0);
   if (threadIdx.x == 0) win_setup(wtab, xn, fs, cf, tp[f], 1.5, FT);
   wh::sync<FT>();
-#if WH_LOVE_REGWIN
   {
     // the frame's samples stay in registers from the gather through both walks (round 6): parked in LDS between them, the
     // window cost a store and two reads per sample on an LDS pipe this kernel keeps busy all the time
@@ -517,9 +472,6 @@ __global__ __launch_bounds__(ft_love(NLT)) void love_train_kernel(
 #pragma unroll
     for (int q = 0; q < NLT / FT; ++q) zr[WH_TID + q * FT] = v[q];
   }
-#else
-  d4c_window<true, NLT, false, 1, FT>(xu, wtab, win_thread_phase(wtab[9]), scratch, zr, [&](int j, double val) { zr[j] = val; });
-#endif
   wh::sync<FT>();
   wh::rfft_lds<NLT, FT, FT, WH_LOVE_MAXR>(zb, tw);  // (66 VGPRs here: the radix-8 plan fits, unlike in d4c_kernel)
   const int b0 = (int)(ceil(100.0 / (fs / NLT)) + 1);
@@ -555,9 +507,6 @@ __global__ __launch_bounds__(ft_love(NLT)) void love_train_kernel(
 // x[q], q < PER: the thread's share of the K values (bit q of `valid` set where the slot is used — any assignment of the
 // values to threads will do).  work: >= 80 ints + K doubles of free
 // LDS; scratch: 32 doubles.  Four barrier phases.
-#ifndef WH_D4C_SEL_PACKED
-#define WH_D4C_SEL_PACKED 1
-#endif
 // 64-lane sum of a 32-bit integer on the VALU (the DPP ladder of wh::wave_sum), result uniform
 __device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
   v += (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
@@ -574,7 +523,6 @@ __device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
 // waiting for the VALU-written mask.
 template <int WIN, int PER, class Digit>
 __device__ __forceinline__ void wave_digit_counts(Digit digit, int (&mine)[WIN]) {
-#if WH_D4C_SEL_PACKED
   static_assert(WIN % 2 == 0, "two digit values per register");
   unsigned c[WIN / 2];
 #pragma unroll
@@ -591,15 +539,6 @@ __device__ __forceinline__ void wave_digit_counts(Digit digit, int (&mine)[WIN])
     mine[2 * j] = (int)(ssum & 0xFFFF);
     mine[2 * j + 1] = (int)(ssum >> 16);
   }
-#else
-#pragma unroll
-  for (int e = 0; e < WIN; ++e) {
-    int cc = 0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) cc += __popcll(__ballot(digit(q) == e));
-    mine[e] = cc;
-  }
-#endif
 }
 
 template <int K, int FT, int PER>
@@ -1025,33 +964,16 @@ __device__ __forceinline__ void d4c_frame(
     return;
   }
 
-#if WH_D4C_ABLATE == 1
-  if (threadIdx.x == 0) out[f * (int64_t)(k_spec > 0 ? k_spec : nap + 2)] = pw[0];
-  return;
-#endif
   STAGE_MARK(0)
   // ---- static centroid from two frames at +-T0/4 (d4c.py:132-142) ---------------------------------------
-#if WH_D4C_CENT_LOOP
-  // ONE copy of the centroid frame's code, run twice (cent starts at 0: 0 + c == c): the kernel's instruction stream
-  // shrinks by a fifth (66 KB -> 52 KB), below the 64 KB instruction cache that two CUs share
-#pragma unroll 1
-  for (int c = 0; c < 2; ++c) {
-    add_centroid<N>(xu, wtab + (2 + c) * kWinTab, e_frame, buf, cent, false, tw, scratch);
-    STAGE_MARK(1 + c)
-  }
-#else
+  // (one rolled copy of the centroid frame's code, run twice, lost: DESIGN.md §4 round 5)
   add_centroid<N>(xu, wtab + 2 * kWinTab, e_frame, buf, cent, true, tw, scratch);
   STAGE_MARK(1)
   add_centroid<N>(xu, wtab + 3 * kWinTab, e_frame, buf, cent, false, tw, scratch);
   STAGE_MARK(2)
-#endif
   low_band_replica_runs<N>(cent, zr, fs, cf, 1.2 * cf);
   STAGE_MARK(3)
 
-#if WH_D4C_ABLATE == 2
-  if (threadIdx.x == 0) out[f * (int64_t)(k_spec > 0 ? k_spec : nap + 2)] = cent[0] + pw[3];
-  return;
-#endif
   // ---- smoothed power spectrum (d4c.py:157-161) ----------------------------------------------
   if (!FUSED) {
     d4c_window<false, N, false, 1>(xu, wtab + kWinTab, e_frame, scratch, zr, [&](int j, double val) { zr[j] = val; });
@@ -1098,10 +1020,6 @@ __device__ __forceinline__ void d4c_frame(
     if (k0 + r < K) td[k0 + r] = pw[r] - bandv[r] * inv_cf;  // T_D = T_gs - T_gb
   wh::sync<FT>();
 
-#if WH_D4C_ABLATE == 3
-  if (threadIdx.x == 0) out[f * (int64_t)(k_spec > 0 ? k_spec : nap + 2)] = td[threadIdx.x];
-  return;
-#endif
   STAGE_MARK(4)
   // ---- band-wise aperiodicity (d4c.py:192-209) -----------------------------------------------
   const int boundary = lc.boundary;
@@ -1175,20 +1093,11 @@ __device__ __forceinline__ void d4c_frame(
     wh::sync<FT>();  // the spectrum has been read: the lower part of the buffer becomes the selection's work area
     STAGE_MARK(9)
     double s_small, s_total;
-#if WH_D4C_ABLATE == 5  // (timing experiment: no rank selection)
-    s_small = px[0];
-    s_total = px[1] + 1.0 + (double)pvalid;
-#else
     sum_smallest<K, FT, 2 * PJ>(px, pvalid, N / 2 - boundary, zr, scratch, &s_small, &s_total);
-#endif
     if (threadIdx.x == 0) band[b] = -10 * log10(s_small / s_total);
     wh::sync<FT>();
   }
 
-#if WH_D4C_ABLATE == 4
-  if (threadIdx.x == 0) out[f * (int64_t)(k_spec > 0 ? k_spec : nap + 2)] = band[0];
-  return;
-#endif
   STAGE_MARK(5)
   // ---- outputs (d4c.py:56-59 / d4cRequiem.py:40) ---------------------------------------------
   const double tilt = (cf - 100) * 2 / 100;
@@ -1208,31 +1117,14 @@ __device__ __forceinline__ void d4c_frame(
 }
 
 template <int N, bool FUSED>
-__global__ __launch_bounds__(ft_of(N), WH_D4C_PAIR > 1 ? WH_D4C_PAIR_MINW : minblk_of(N)) void d4c_kernel(
+__global__ __launch_bounds__(ft_of(N), minblk_of(N)) void d4c_kernel(
     const double* __restrict__ x, const int64_t* __restrict__ x_off, const int32_t* __restrict__ frame_utt,
     const double* __restrict__ tp, double* __restrict__ f0_io, const double* __restrict__ vuv,
     const int32_t* __restrict__ gate, double threshold, double fs, int nap, int interval,
     const double* __restrict__ window, int wlen, const double2* __restrict__ tw_base, int k_spec,
     double* __restrict__ out, double* __restrict__ coarse_dbg, long long n_frames, D4cLaunchConst lc) {
-#if WH_D4C_PAIR > 1
-  // (experiment) WH_D4C_PAIR neighbouring frames per workgroup, one after the other
-  const long long n_units = (n_frames + WH_D4C_PAIR - 1) / WH_D4C_PAIR;
-  const long long unit = wh::xcd_unit(blockIdx.x, n_units);
-  if (unit >= n_units) return;
-#if defined(WH_D4C_PAIR_ROLLED) && WH_D4C_PAIR_ROLLED
-#pragma unroll 1  // one copy of the frame's code (two copies are 130 KB: twice the instruction cache two CUs share)
-#else
-#pragma unroll
-#endif
-  for (int rep = 0; rep < WH_D4C_PAIR; ++rep) {
-    d4c_frame<N, FUSED>(x, x_off, frame_utt, tp, f0_io, vuv, gate, threshold, fs, nap, interval, window, wlen, tw_base, k_spec,
-                        out, coarse_dbg, n_frames, lc, unit * WH_D4C_PAIR + rep);
-    __syncthreads();
-  }
-#else
   d4c_frame<N, FUSED>(x, x_off, frame_utt, tp, f0_io, vuv, gate, threshold, fs, nap, interval, window, wlen, tw_base, k_spec, out,
                       coarse_dbg, n_frames, lc, wh::xcd_unit(blockIdx.x, n_frames));
-#endif
 }
 
 int pow2_at_least(double v) { return (int)llround(pow(2.0, ceil(log2(v)))); }
@@ -1264,7 +1156,7 @@ int launch_main(wh_ctx* ctx, hipStream_t st, const wh_batch* b, const double* x,
                 int wlen, int k_spec, double* out, double* coarse) {
   const size_t lds = sizeof(double) * (2 * N + 40 + 8 + 4 * kWinTab);
   if (int rc = wh::allow_lds(&d4c_kernel<N, FUSED>, lds)) return rc;
-  { wh::KernelTimer _kt(ctx, st, "d4c_kernel"); hipLaunchKernelGGL((d4c_kernel<N, FUSED>), dim3((unsigned)wh::xcd_grid((b->total_frames + WH_D4C_PAIR - 1) / WH_D4C_PAIR)), dim3(ft_of(N)), lds, st, x, b->d_x_off,
+  { wh::KernelTimer _kt(ctx, st, "d4c_kernel"); hipLaunchKernelGGL((d4c_kernel<N, FUSED>), dim3((unsigned)wh::xcd_grid(b->total_frames)), dim3(ft_of(N)), lds, st, x, b->d_x_off,
                      b->d_frame_utt, tp, f0, vuv, gate, thr, fs, nap, interval, win, wlen, ctx->d_twiddle, k_spec, out,
                      coarse, (long long)b->total_frames, d4c_launch_const(fs, N, wlen, interval, nap)); }
   WH_LAUNCH_CHECK("d4c_kernel");

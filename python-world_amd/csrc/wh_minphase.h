@@ -1,0 +1,149 @@
+// The minimum-phase chain shared by the pulse responses (wh_synthesis.hip) and the Requiem filter (wh_requiem.hip): the
+// transcendentals of its loops as real calls, and min_phase_response.  Its arithmetic may fuse a*b+c into one FP64
+// instruction (the library is built with -ffp-contract=off): the outputs are compared with the reference at tolerances.
+// Include after wh_math.h and wh_device.h (with the unit's opaque WH_TID).
+#pragma once
+#include <type_traits>
+
+namespace {
+
+#ifndef WH_FT_SYNTH
+#define WH_FT_SYNTH 256
+#endif
+// Threads cooperating on one pulse / frame: 256 up to N = 1024, 512 from N = 2048 (44.1 / 48 kHz), where the 54 KB
+// of LDS per pulse leave two workgroups per CU and the thread count is the occupancy (measured 58.6 -> 50.5 ms on
+// config 5).
+constexpr int ft_syn(int n) { return n >= 2048 ? 2 * WH_FT_SYNTH : WH_FT_SYNTH; }
+
+// Transcendentals of the per-pulse loop as real calls: inlined, their polynomial coefficients (64-bit literals live in
+// VGPR pairs) are loop invariants of response_kernel's pulse loop and get parked in registers across the whole body.
+// (exp(a0) cos(pi b0), exp(a0) sin(pi b0), exp(a1) cos(pi b1), exp(a1) sin(pi b1)): two bins of a minimum-phase spectrum
+__device__ __attribute__((noinline)) double4 cis_pair_call(double a0, double b0, double a1, double b1) {
+  const double e0 = exp(a0), e1 = exp(a1);
+  double s0, c0, s1, c1;
+  sincospi(b0, &s0, &c0);
+  sincospi(b1, &s1, &c1);
+  return make_double4(e0 * c0, e0 * s0, e1 * c1, e1 * s1);
+}
+__device__ __attribute__((noinline)) double2 log_pair_call(double x, double y) { return make_double2(wh::flog(x), wh::flog(y)); }
+__device__ __attribute__((noinline)) double log_call(double x) { return wh::flog(x); }
+// (wh::fexp / wh::fsincospi are no shorter than the library's once the compiler has materialised their coefficients — 66 / 75
+// instructions against 56 / 82 — and read as a scalar table they stall on its latency: measured, not used)
+
+// Minimum-phase response (synthesis.py:100-116; synthesisRequiem.py:112-118) from the mirrored log-amplitude to the time
+// domain, with the O(N) passes between the three transforms fused:
+//   in : zr[n] = log|S[min(n, N-n)]| / 2, n < N (real, even), visible;  out: time-domain response N * h[n] in zr.
+//   (1) forward transform of a real EVEN sequence: its spectrum is real, so the post-pass of the half-size transform
+//       computes real parts only, and writes them where the next transform wants them — folded onto the upper half,
+//       doubled (cepstrum fold) — instead of: post-pass -> copy real parts -> fold (three LDS round trips, three barriers);
+//   (2) after the second transform a thread holds the pair of bins (k, N/2-k) in registers through the post-pass, the
+//       complex exponential AND the pre-pass of the inverse real transform: exp(r.x/N) * cis(-r.y/N - delay*k), where
+//       `delay_pi` (units of pi per bin) is the pulse's fractional delay — the reference multiplies the spectrum by
+//       exp(-i*coef*shift*k) afterwards (synthesis.py:61-64); folding it into the angle saves one sincospi and one
+//       complex product per bin, and the four passes over the half spectrum become one.
+// `mul(k, E)`: what the minimum-phase bin k (0 <= k <= N/2) is multiplied with before the inverse transform — identity
+// for the pulse responses, the excitation frame's spectrum in the Requiem filter (synthesisRequiem.py:112-118).
+// The chain's three 512-point transforms (N = 1024, the 16 kHz shape): WAVE puts each on one wave of its GT-thread group
+// (wh::fft_lds_wave: one barrier per transform where the workgroup-wide plan takes six; the voiced chains' plan and bits
+// are unchanged, an unvoiced pulse's single chain goes from 4-4-4-4-2 on two waves to 8-8-8 on one).  Other lengths and
+// the Requiem filter keep the workgroup-wide plans.
+template <int M, bool INV, int GT, int FT, bool WAVE>
+__device__ __forceinline__ void mp_fft(wh::ckp<double2> zb, wh::ckp<const double2> tw) {
+  if constexpr (WAVE) wh::fft_lds_wave<M, INV, GT, FT>(zb, tw);
+  else wh::fft_lds<M, INV, GT, FT>(zb, tw);
+}
+struct SpectrumIdentity {
+  __device__ __forceinline__ double2 operator()(int, double2 e) const { return e; }
+};
+// `side(i, n)`: a job for the waves that a WAVE chain's FIRST transform leaves without butterflies (wh::fft_lds_wave) —
+// the pulse's noise run in response_pulse.  NoSide: they go straight to the transform's barrier.
+struct NoSide {};
+template <int N, int GT, bool WAVE = false, class Mul = SpectrumIdentity, class Side = NoSide>
+__device__ __forceinline__ void min_phase_response(wh::ckp<double2> zb, wh::ckp<const double2> tw_base, double delay_pi, Mul mul = Mul(),
+                                                   Side side = Side()) {
+#pragma clang fp contract(fast)
+  constexpr int FT = ft_syn(N);
+  constexpr int M = N / 2;
+  constexpr int PP = (M / 2 + 1 + GT - 1) / GT;  // bin pairs (k, M-k), k <= M/2, per thread
+  const wh::ckp<double> zr = wh::ck_as<double>(zb);
+  const int gt = WH_TID & (GT - 1);
+  const wh::ckp<const double2> WH_RESTRICT w = tw_base + N;
+  if constexpr (WAVE && !std::is_same<Side, NoSide>::value) wh::fft_lds_wave<M, false, GT, FT>(zb, tw_base + M, side);
+  else mp_fft<M, false, GT, FT, WAVE>(zb, tw_base + M);
+  {
+    double ck[PP], cm[PP];
+#pragma unroll
+    for (int p = 0; p < PP; ++p) {
+      const int k = gt + p * GT;
+      ck[p] = cm[p] = 0.0;
+      if (k <= M / 2) {
+        const double2 a = zb[k], b = zb[M - k];
+        if (k == 0) {
+          ck[p] = a.x + a.y;
+          cm[p] = a.x - a.y;
+        } else {
+          const double er = 0.5 * (a.x + b.x), dr = 0.5 * (a.x - b.x), di = 0.5 * (a.y + b.y);
+          const double2 wk = wh::ldg2(w + k);
+          const double tr = fma(wk.x, di, wk.y * dr);
+          ck[p] = er + tr;  // Re X[k]
+          cm[p] = er - tr;  // Re X[M-k]
+        }
+      }
+    }
+    wh::sync<FT>();  // every pair has been read
+#pragma unroll
+    for (int p = 0; p < PP; ++p) {
+      const int k = gt + p * GT;
+      if (k <= M / 2) {
+        if (k == 0) {
+          zr[0] = ck[p];
+          zr[M] = 2 * cm[p];
+        } else {
+          zr[N - k] = 2 * ck[p];
+          zr[M + k] = 2 * cm[p];  // (k = M/2: the same slot, the same value)
+        }
+      }
+    }
+    for (int n = 1 + gt; n < M; n += GT) zr[n] = 0.0;
+    wh::sync<FT>();
+  }
+  mp_fft<M, false, GT, FT, WAVE>(zb, tw_base + M);
+#pragma unroll 1
+  for (int k = gt; k <= M / 2; k += GT) {
+    const double2 a = zb[k], b = zb[M - k];
+    double2 x0, x1;  // R[k], R[M-k]: spectrum of the folded cepstrum
+    const double2 wk = wh::ldg2(w + k);
+    if (k == 0) {
+      x0 = make_double2(a.x + a.y, 0.0);
+      x1 = make_double2(a.x - a.y, 0.0);
+    } else {
+      const double er = 0.5 * (a.x + b.x), ei = 0.5 * (a.y - b.y);
+      const double dr = 0.5 * (a.x - b.x), di = 0.5 * (a.y + b.y);
+      const double tr = fma(wk.x, di, wk.y * dr);
+      const double ti = fma(wk.y, di, -(wk.x * dr));
+      x0 = make_double2(er + tr, ei + ti);
+      x1 = make_double2(er - tr, ti - ei);
+    }
+    // minimum-phase spectrum exp(conj(R) / N) with the fractional delay in the angle (both in units of pi)
+    // the pair of bins through ONE call: the library's exp / sincospi spend a third of their instructions putting polynomial
+    // coefficients into registers, and two evaluations inside one function share them
+    const double4 cis = cis_pair_call(x0.x / N, -x0.y / N * M_1_PI - delay_pi * (double)k, x1.x / N,
+                                      -x1.y / N * M_1_PI - delay_pi * (double)(M - k));
+    double2 A = mul(k, make_double2(cis.x, cis.y)), B = mul(M - k, make_double2(cis.z, cis.w));
+    if (k == 0) {  // DC and Nyquist bins: only their real parts reach a real output
+      A.y = 0.0;
+      B.y = 0.0;
+    }
+    // pre-pass of the inverse real transform (wh::irfft_lds) on the pair
+    const double er = A.x + B.x, ei = A.y - B.y;
+    const double dr = A.x - B.x, di = A.y + B.y;
+    const double orr = fma(dr, wk.x, di * wk.y);
+    const double oi = fma(di, wk.x, -(dr * wk.y));
+    zb[k] = make_double2(er - oi, ei + orr);
+    if (k != 0) zb[M - k] = make_double2(er + oi, orr - ei);
+  }
+  wh::sync<FT>();
+  mp_fft<M, true, GT, FT, WAVE>(zb, tw_base + M);
+}
+
+}  // namespace

@@ -1,4 +1,4 @@
-"""CPU: a NumPy model of the tile-parallel exact phase scan (python-world_amd/csrc/wh_synthesis.hip: xs_*_kernel) —
+"""CPU: a NumPy model of the tile-parallel exact phase scan (python-world_amd/csrc/wh_timebase.hip: xs_*_kernel) —
 the argument that makes np.cumsum parallel, checked bit for bit without a GPU.
 
 Sequential semantics: a[j+1] = fl(a[j] + x[j]), x >= 0.  While a stays in one binade [2^k, 2^(k+1)) every partial sum is

@@ -73,10 +73,10 @@ CALL_SITES = {
     ("wh_d4c.hip", "fft_lds"): 3,
     ("wh_d4c.hip", "fft_lds_from_regs"): 2,
     ("wh_d4c.hip", "rfft_lds"): 2,
+    ("wh_minphase.h", "fft_lds"): 1,
+    ("wh_minphase.h", "fft_lds_wave"): 2,
+    ("wh_requiem.hip", "rfft_lds"): 1,
     ("wh_swipe.hip", "rfft_lds"): 1,
-    ("wh_synthesis.hip", "fft_lds"): 1,
-    ("wh_synthesis.hip", "fft_lds_wave"): 2,
-    ("wh_synthesis.hip", "rfft_lds"): 1,
 }
 
 

@@ -43,7 +43,7 @@ def test_encode_is_bitwise_deterministic(method, requiem):
 @pytest.mark.parametrize("requiem", [False, True])
 def test_decode_is_bitwise_deterministic(requiem):
     """The overlap-add of the pulse responses / Requiem frames is summed in a fixed order (rows of runs of pulses /
-    frames, then a gather in run order: wh_synthesis.hip RunState, req_filter_kernel) — no atomics since round 5, so the
+    frames, then a gather in run order: wh_synthesis.hip RunState, wh_requiem.hip req_filter_kernel) — no atomics since round 5, so the
     decode repeats bit for bit (rounds 1-4: equal up to the order of the FP64 atomics, 1e-17)."""
     from world.batch import WorldBatch
 

@@ -368,7 +368,7 @@ def test_encoding_dict_materialises_on_read_and_remembers_it():
 def test_philox_seed_for_offset_rekeys_the_utterance_streams():
     """World.decode_batch renders a large batch in consecutive parts; utterance u of a part that starts at utterance
     `base` must draw the noise of utterance base + u of the whole batch.  The device keys a stream with
-    seed * A + u * B + 1 mod 2**64 (philox_key, csrc/wh_synthesis.hip:837): the shifted seed solves that for every u."""
+    seed * A + u * B + 1 mod 2**64 (philox_key, csrc/wh_synthesis.hip): the shifted seed solves that for every u."""
     from world.synthesis import _PHILOX_SEED_MUL as A, _PHILOX_UTT_MUL as B, philox_seed_for_offset
 
     src = open(os.path.join(os.path.dirname(__file__), "..", "python-world_amd", "csrc", "wh_synthesis.hip")).read()

@@ -7,7 +7,7 @@ in NumPy against the form the reference computes (no GPU involved; the GPU suite
   * band_taps_fft_kernel / band_events_ols_kernel (wh_bands.h): a Harvest band filter (harvest.py:253-256) is symmetric
     about its centre tap, so rotated to put that tap at index 0 its spectrum is real; multiplying the tile spectrum by the
     real spectrum and reading the outputs half a filter length earlier is the reference's band-passed signal.
-  * req_excite_kernel (wh_synthesis.hip): the periodic Requiem excitation (synthesisRequiem.py:51-61) gathered per output
+  * req_excite_kernel (wh_requiem.hip): the periodic Requiem excitation (synthesisRequiem.py:51-61) gathered per output
     sample from the pulses that cover it, with the reference's clipped fancy-index semantics (only the last tap written
     to a clipped index survives), equals the scatter the reference performs — bit for bit, the sums run in pulse order
     either way — and the 64-ary wave search that finds a tile's first pulse is np.searchsorted(side='left')."""
@@ -123,7 +123,7 @@ def test_zero_phase_tap_spectrum_is_real_and_filters_like_the_reference(bf):
 
 # ---- gathered Requiem excitation ---------------------------------------------------------------------------------------
 def _first_pulse_at(pi, lo):
-    """The 64-ary search of first_pulse_at (wh_synthesis.hip), lane by lane."""
+    """The 64-ary search of first_pulse_at (wh_syn_types.h), lane by lane."""
     base, n = 0, len(pi)
     while n > 0:
         stride = (n + 63) // 64

@@ -1,5 +1,5 @@
 // Micro-benchmark: cost per element of a single-lane dependent FP64 add chain with different LDS traffic
-// patterns around it (sizing the exact phase scan of wh_synthesis.hip).  hipcc --offload-arch=gfx950 -O3 chain.hip
+// patterns around it (sizing the exact phase scan of wh_timebase.hip).  hipcc --offload-arch=gfx950 -O3 chain.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
