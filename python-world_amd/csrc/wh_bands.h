@@ -7,6 +7,7 @@
 #pragma once
 #include "wh_events.h"
 #include "wh_host.h"
+#include "wh_hv_types.h"  // kOlsN, kOlsValid: the overlap-save geometry, which also sizes Harvest's workspace
 
 namespace wh {
 
@@ -53,6 +54,8 @@ __device__ __forceinline__ int zmap(int i, int pl) {
 }
 
 // s[g] = sum_k taps[k] * z[(bias + 1 + g) - k], g in [0, M)
+// (FMA: instantiated at true only — both callers hand over odd tap counts and take the register-tiled path; the parameter
+// stays because it is part of the kernel's name, which profiles key on)
 template <bool FMA>
 __global__ __launch_bounds__(256) void band_events_kernel(const BandJob* __restrict__ jobs, int pad,
                                                           const double* __restrict__ taps_all,
@@ -190,18 +193,11 @@ static __global__ __launch_bounds__(256) void band_concat_kernel(const BandJob* 
 
 inline int launch_band_events(wh_ctx* ctx, hipStream_t st, const BandJob* d_jobs, int nb, int n_utt, int pad,
                               const double* d_taps, const int32_t* d_tap_off, const int32_t* d_tap_len,
-                              const int32_t* d_bias, int max_lb, bool use_fma, int32_t* d_flag, int nseg = 1) {
-  const size_t lds_tiled = sizeof(double) * (((max_lb + 1) & ~1) + kBandPlanes * band_plane_len(kBandTileR + 2 + max_lb) +
-                                             kBandTileR + 2) + 64;
-  const size_t lds_plain = sizeof(double) * (((max_lb + 1) & ~1) + ((kBandTile + 2 + max_lb + 1) & ~1) + kBandTile + 2) + 64;
-  const size_t lds = use_fma ? lds_tiled : lds_plain;
-  if (use_fma) {
-    if (int rc = allow_lds(&band_events_kernel<true>, lds)) return rc;
-    { KernelTimer _kt(ctx, st, "band_events_kernel"); hipLaunchKernelGGL(band_events_kernel<true>, dim3(nb, n_utt, nseg), dim3(256), lds, st, d_jobs, pad, d_taps, d_tap_off, d_tap_len, d_bias, nb, d_flag); }
-  } else {
-    if (int rc = allow_lds(&band_events_kernel<false>, lds)) return rc;
-    { KernelTimer _kt(ctx, st, "band_events_kernel"); hipLaunchKernelGGL(band_events_kernel<false>, dim3(nb, n_utt, nseg), dim3(256), lds, st, d_jobs, pad, d_taps, d_tap_off, d_tap_len, d_bias, nb, d_flag); }
-  }
+                              const int32_t* d_bias, int max_lb, int32_t* d_flag, int nseg = 1) {
+  const size_t lds = sizeof(double) * (((max_lb + 1) & ~1) + kBandPlanes * band_plane_len(kBandTileR + 2 + max_lb) +
+                                       kBandTileR + 2) + 64;
+  if (int rc = allow_lds(&band_events_kernel<true>, lds)) return rc;
+  { KernelTimer _kt(ctx, st, "band_events_kernel"); hipLaunchKernelGGL(band_events_kernel<true>, dim3(nb, n_utt, nseg), dim3(256), lds, st, d_jobs, pad, d_taps, d_tap_off, d_tap_len, d_bias, nb, d_flag); }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail("band_events_kernel", e);
   if (nseg > 1) {
@@ -226,35 +222,18 @@ inline int launch_band_events(wh_ctx* ctx, hipStream_t st, const BandJob* d_jobs
 // one pass (emit_crossings_block).  The inverse transform is left unnormalised: the crossing detector only looks at
 // signs and ratios.
 // ------------------------------------------------------------------------------------------------------------
-#ifndef WH_OLS_MINW
-#define WH_OLS_MINW 3  // waves per SIMD the channel walker's register allocation leaves room for (168 VGPRs; the walker
-                       // needs 169 with the thread index read opaquely — wh_harvest.hip — and ~310 without: 2 -> 4.45 ms,
-                       // 3 -> 3.7 ms at config 3)
-#endif
-#ifndef WH_OLS_FUSED_PRE
-#define WH_OLS_FUSED_PRE 1
-#endif
-#ifndef WH_OLS_N
-#define WH_OLS_N 4096
-#endif
-constexpr int kOlsN = WH_OLS_N;
-#ifndef WH_OLS_VALID
-#define WH_OLS_VALID 3584
-#endif
-constexpr int kOlsValid = WH_OLS_VALID;  // outputs kept per block: 256 x 14 positions (+2 look-ahead samples); the longest
-                                         // filter (493 taps) leaves 4096 - 495 = 3601
+// waves per SIMD the channel walker's register allocation leaves room for (168 VGPRs; the walker needs 169 with the thread
+// index read opaquely — wh_tid.h — and ~310 without: 2 -> 4.45 ms, 3 -> 3.7 ms at config 3)
+constexpr int kOlsMinWaves = 3;
 constexpr int kOlsPer = kOlsValid / 256;
-#ifndef WH_OLS_BANDS
-#define WH_OLS_BANDS 1  // 1 (round 6): one channel per workgroup at every batch size; 4: four; 0: by batch size (rounds 4-5)
-#endif
-// Channels per workgroup of band_events_ols_kernel (they share the tile spectrum of each tile): a template parameter.
-// ONE (round 6, every batch size): the channel's tap spectrum stays in registers for all tiles, and with the XCD-aware
-// workgroup order the tile spectra come out of the L2 the utterance's other channels share.  Four channels per workgroup
-// were 1 ms faster at 1024 utterances (40.7 against 41.7 ms) but re-read their tap spectra per tile — and the 16 GB
+// Channels per workgroup of band_events_ols_kernel (they share the tile spectrum of each tile): a template parameter,
+// instantiated at ONE (round 6, every batch size): the channel's tap spectrum stays in registers for all tiles, and with the
+// XCD-aware workgroup order the tile spectra come out of the L2 the utterance's other channels share.  Four channels per
+// workgroup were 1 ms faster at 1024 utterances (40.7 against 41.7 ms) but re-read their tap spectra per tile — and the 16 GB
 // stream of edge stores kept pushing those (and the tile spectra) out of L2: 36.0 GB of HBM traffic per launch against
 // 20.0 GB (profiles/r06_*; non-temporal edge stores stop the evictions but, scattered 8-byte writes, double the bytes
-// written: 38.6 GB; collected in LDS and written as whole non-temporal runs: 20.0 GB but 44.5 ms).
-constexpr int kOlsBands = 4;  // band_events_ols2_kernel (the pair variant); band_events_ols_kernel is templated on it
+// written: 38.6 GB; collected in LDS and written as whole non-temporal runs: 20.0 GB but 44.5 ms).  Two channels per inverse
+// transform (one full-size complex transform for a pair) lost too: 7.2 against 6.7 ms at config 3.
 
 // T_b = rfft(taps_b zero-padded to kOlsN): [nb][kOlsN/2+1] complex (the fused front end's product), and
 // R_b = the same transform of the taps rotated so that their centre tap sits at index 0: [nb][kOlsN/2+1] REAL.  A band
@@ -312,11 +291,8 @@ static __global__ __launch_bounds__(256) void band_tile_fft_kernel(const BandJob
   for (int k = threadIdx.x; k <= kOlsN / 2; k += 256) out[k] = z[k];
 }
 
-#ifndef WH_OLS_XCD
-#define WH_OLS_XCD 1
-#endif
 template <int kOlsBands>
-static __global__ __launch_bounds__(256, WH_OLS_MINW) void band_events_ols_kernel(const BandJob* __restrict__ jobs, int nb, int n_utt, int n_xcd, int H,
+static __global__ __launch_bounds__(256, kOlsMinWaves) void band_events_ols_kernel(const BandJob* __restrict__ jobs, int nb, int n_utt, int n_xcd, int H,
                                                                      const int32_t* __restrict__ half,
                                                                      const double* __restrict__ tspec,
                                                                      const double2* __restrict__ zspec,
@@ -328,7 +304,6 @@ static __global__ __launch_bounds__(256, WH_OLS_MINW) void band_events_ols_kerne
   double2* ybuf = reinterpret_cast<double2*>(smem);
   double* sig_all = reinterpret_cast<double*>(smem);
   unsigned long long* scan_scratch = reinterpret_cast<unsigned long long*>(ybuf + KS + 1);  // 8
-#if WH_OLS_XCD
   // Workgroup -> (utterance, channel group), XCD-aware (round 6).  Every channel group of an utterance walks the SAME tile
   // spectra (754 KB per 10 s utterance); with the groups of an utterance dealt over the whole launch (utterance-fastest
   // order, rounds 2-5) each of them fetched its own copy from HBM: 38 x 0.77 GB = 29 GB of the 46.5 GB this kernel moved
@@ -343,13 +318,6 @@ static __global__ __launch_bounds__(256, WH_OLS_MINW) void band_events_ols_kerne
   const int u = (local / groups) * n_xcd + xcd;
   if (u >= n_utt) return;
   const int b0 = (local % groups) * kOlsBands;
-#else
-  // utterance-fastest workgroup order: the workgroups in flight at any time share a few channel groups, so the
-  // 33 KB tap spectra they stream stay in every XCD's L2 (channel-fastest, each XCD cycled through all 5 MB of them
-  // and half of the 8.6 GB requested per launch came from HBM)
-  const int u = blockIdx.x;
-  const int b0 = blockIdx.y * kOlsBands;
-#endif
   const BandJob job0 = jobs[(int64_t)u * nb + b0];
   const int64_t M = job0.M;
   const int64_t tiles = (M + kOlsValid - 1) / kOlsValid;
@@ -362,7 +330,6 @@ static __global__ __launch_bounds__(256, WH_OLS_MINW) void band_events_ols_kerne
   // Software pipeline over (tile, channel): the tap spectrum of the next channel and, behind a tile's last channel, the
   // next tile's spectrum are fetched while the current channel's crossings are extracted — the one stretch of the
   // loop that needs few registers — so neither load's L2 latency (33 KB per channel-tile) sits in front of a product.
-#if WH_OLS_FUSED_PRE
   // A thread holds the bins k = tid + 256 q (q < 4) of the two spectra TOGETHER WITH their mirrors N/2 - k (and the
   // self-paired bin N/4): the product and the real transform's pre-pass (irfft_lds: Z[k] = 2E + i 2O from Y[k] and
   // Y[N/2 - k]) then happen in registers and the buffer is written once, already as the half-size complex sequence —
@@ -396,25 +363,6 @@ static __global__ __launch_bounds__(256, WH_OLS_MINW) void band_events_ols_kerne
     }
     dst[2 * PQ] = src[NH / 2];
   };
-#else
-  constexpr int PER = (KS + 255) / 256;  // 9 per thread
-  double2 zr[PER];
-  double tr[PER];
-  auto load_taps = [&](double (&dst)[PER], const double* src) {
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int k = threadIdx.x + q * 256;
-      dst[q] = k < KS ? src[k] : 0.0;
-    }
-  };
-  auto load_spec = [&](double2 (&dst)[PER], const double2* src) {
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int k = threadIdx.x + q * 256;
-      dst[q] = k < KS ? src[k] : make_double2(0.0, 0.0);
-    }
-  };
-#endif
   auto scale = [](double2 z, double t) { return make_double2(z.x * t, z.y * t); };
   const int n_ch = nb - b0 < kOlsBands ? nb - b0 : kOlsBands;
   load_spec(zr, zspec + tile_off[u] * KS);
@@ -430,7 +378,6 @@ static __global__ __launch_bounds__(256, WH_OLS_MINW) void band_events_ols_kerne
       int base_cnt[4];
 #pragma unroll
       for (int t = 0; t < 4; ++t) base_cnt[t] = s_cnt[g][t];
-#if WH_OLS_FUSED_PRE
       {
         const double2* __restrict__ w = tw_base + kOlsN;
         auto fold = [&](double2 a, double2 bb, double2 wk, double2* lo, double2* hi) {
@@ -462,18 +409,7 @@ static __global__ __launch_bounds__(256, WH_OLS_MINW) void band_events_ols_kerne
         }
       }
       sync_lds<256>();
-#if WH_OLS_ABLATE != 1
       fft_lds<NH, true, 256>(ybuf, tw_base + NH);
-#endif
-#else
-#pragma unroll
-      for (int q = 0; q < PER; ++q) {
-        const int k = threadIdx.x + q * 256;
-        if (k < KS) ybuf[k] = scale(zr[q], tr[q]);
-      }
-      sync_lds<256>();
-      irfft_lds<kOlsN, 256>(ybuf, tw_base);
-#endif
       if (g + 1 < n_ch) {
         load_taps(tr, tspec + (int64_t)(b + 1) * KS);
       } else {
@@ -483,13 +419,8 @@ static __global__ __launch_bounds__(256, WH_OLS_MINW) void band_events_ols_kerne
       // output i of the block is s[t0 + i - (H + 1)]: the tile's outputs start at index H + 1 (H + h + 1 with the taps as
       // they lie; the zero-phase rotation of band_taps_fft_kernel advances the output by the half length h)
       const double* sig = sig_all + (H + 1);
-#if WH_OLS_ABLATE == 1 || WH_OLS_ABLATE == 2
-      __syncthreads();
-      if (sig[threadIdx.x * kOlsPer] == 1.2345e300) stg(job.edges, sig[threadIdx.x]);  // (keeps what was computed alive)
-#else
-      emit_crossings_block<1, kOlsPer>(sig, t0, M, job.edges, job.cap, base_cnt, scan_scratch, flags, job.hints, job.hint_spt,
-                                       job.hint_inv_spt, job.hint_tiles, job.hint_stride);
-#endif
+      emit_crossings_block<kOlsPer>(sig, t0, M, job.edges, job.cap, base_cnt, scan_scratch, flags, job.hints, job.hint_spt,
+                                    job.hint_inv_spt, job.hint_tiles, job.hint_stride);
       __syncthreads();
       if (threadIdx.x < 4) s_cnt[g][threadIdx.x] = base_cnt[threadIdx.x];
     }
@@ -507,87 +438,6 @@ static __global__ __launch_bounds__(256, WH_OLS_MINW) void band_events_ols_kerne
   }
 }
 
-// Two channels per inverse transform.  The filtered tiles y_a, y_b of two channels are real, so the complex sequence
-// y_a + i*y_b is the inverse DFT of Y_a + i*Y_b (Hermitian extensions): ONE full-size complex inverse FFT (four
-// radix-8 passes, two butterflies per thread) instead of two half-size ones with their extra real-transform pass —
-// half the barrier phases per channel, and the split into the two channels is free (real and imaginary parts).  The
-// crossing detector then reads one component of the interleaved buffer (stride 2).
-static __global__ __launch_bounds__(256, 2) void band_events_ols2_kernel(const BandJob* __restrict__ jobs, int nb, int H,
-                                                                      const int32_t* __restrict__ half,
-                                                                      const double2* __restrict__ tspec,
-                                                                      const double2* __restrict__ zspec,
-                                                                      const int64_t* __restrict__ tile_off,
-                                                                      const double2* __restrict__ tw_base,
-                                                                      int32_t* __restrict__ flags) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int KS = kOlsN / 2 + 1;
-  constexpr int PER = (KS + 255) / 256;
-  double2* ybuf = reinterpret_cast<double2*>(smem);  // kOlsN complex
-  const double* comp = reinterpret_cast<const double*>(smem);
-  unsigned long long* scan_scratch = reinterpret_cast<unsigned long long*>(ybuf + kOlsN);  // 8
-  // utterance-fastest workgroup order: the workgroups in flight at any time share a few channel groups, so the
-  // 33 KB tap spectra they stream stay in every XCD's L2 (channel-fastest, each XCD cycled through all 5 MB of them
-  // and half of the 8.6 GB requested per launch came from HBM)
-  const int u = blockIdx.x;
-  const int b0 = blockIdx.y * kOlsBands;
-  const int64_t M = jobs[(int64_t)u * nb + b0].M;
-  const int64_t tiles = (M + kOlsValid - 1) / kOlsValid;
-  __shared__ int s_cnt[kOlsBands][4];
-  if (threadIdx.x < kOlsBands * 4) s_cnt[threadIdx.x >> 2][threadIdx.x & 3] = 0;
-  __syncthreads();
-#pragma unroll 1
-  for (int64_t tile = 0; tile < tiles; ++tile) {
-    const int64_t t0 = tile * kOlsValid;
-    double2 zr[PER];
-    const double2* zs = zspec + (tile_off[u] + tile) * KS;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int k = threadIdx.x + q * 256;
-      zr[q] = k < KS ? zs[k] : make_double2(0.0, 0.0);
-    }
-#pragma unroll 1
-    for (int g = 0; g < kOlsBands; g += 2) {
-      const int ba = b0 + g;
-      if (ba >= nb) break;
-      const bool has_b = ba + 1 < nb;
-      const double2* ta = tspec + (int64_t)ba * KS;
-      const double2* tb = tspec + (int64_t)(has_b ? ba + 1 : ba) * KS;
-      __syncthreads();  // the previous pair's crossings have been read out of the buffer
-#pragma unroll
-      for (int q = 0; q < PER; ++q) {
-        const int k = threadIdx.x + q * 256;
-        if (k < KS) {
-          const double2 ya = cmul(zr[q], ta[k]);
-          double2 yb = cmul(zr[q], tb[k]);
-          if (!has_b) yb = make_double2(0.0, 0.0);
-          // Y[k] = Ya[k] + i*Yb[k];  Y[N-k] = conj(Ya[k]) + i*conj(Yb[k])
-          ybuf[k] = make_double2(ya.x - yb.y, ya.y + yb.x);
-          if (k > 0 && k < kOlsN / 2) ybuf[kOlsN - k] = make_double2(ya.x + yb.y, yb.x - ya.y);
-        }
-      }
-      __syncthreads();
-      fft_lds<kOlsN, true, 256>(ybuf, tw_base + kOlsN);
-      for (int c = 0; c < 2; ++c) {
-        const int b = ba + c;
-        if (b >= nb) break;
-        const BandJob job = jobs[(int64_t)u * nb + b];
-        int base_cnt[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) base_cnt[t] = s_cnt[g + c][t];
-        // output i of the block is s[t0 + i - (H + h + 1)]; component c of complex sample i sits at comp[2 i + c]
-        const double* sig = comp + 2 * (H + half[b] + 1) + c;
-        __syncthreads();
-        emit_crossings_block<2, kOlsPer>(sig, t0, M, job.edges, job.cap, base_cnt, scan_scratch, flags);
-        __syncthreads();
-        if (threadIdx.x < 4) s_cnt[g + c][threadIdx.x] = base_cnt[threadIdx.x];
-      }
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < kOlsBands * 4 && b0 + (threadIdx.x >> 2) < nb)
-    jobs[(int64_t)u * nb + b0 + (threadIdx.x >> 2)].counts[threadIdx.x & 3] = s_cnt[threadIdx.x >> 2][threadIdx.x & 3];
-}
-
 // ws_spec: device scratch of (n_bands + total_tiles) * (kOlsN/2+1) complex; h_tile_off[n_utt+1] tile offsets (HOST).
 inline int launch_band_events_ols(wh_ctx* ctx, hipStream_t st, const BandJob* d_jobs, int nb, int n_utt, int pad, int H,
                                   const double* d_taps, const int32_t* d_tap_off, const int32_t* d_tap_len,
@@ -596,33 +446,13 @@ inline int launch_band_events_ols(wh_ctx* ctx, hipStream_t st, const BandJob* d_
   const size_t lds_fft = sizeof(double) * (kOlsN + 2);
   { KernelTimer _kt(ctx, st, "band_taps_fft_kernel"); hipLaunchKernelGGL(band_taps_fft_kernel, dim3(nb), dim3(256), lds_fft, st, d_taps, d_tap_off, d_tap_len, ctx->d_twiddle, d_tspec, d_tre); }
   { KernelTimer _kt(ctx, st, "band_tile_fft_kernel"); hipLaunchKernelGGL(band_tile_fft_kernel, dim3((unsigned)max_tiles, n_utt), dim3(256), lds_fft, st, d_jobs, nb, pad, H, d_tile_off, ctx->d_twiddle, d_zspec); }
-#ifndef WH_OLS_PAIR
-#define WH_OLS_PAIR 0  // measured: 7.2 ms against 6.7 ms for the one-channel-per-transform walker at config 3
-#endif
-#if WH_OLS_PAIR
-  const size_t lds = sizeof(double2) * kOlsN + 64;
-  if (int rc = allow_lds(&band_events_ols2_kernel, lds)) return rc;
-  { KernelTimer _kt(ctx, st, "band_events_kernel"); hipLaunchKernelGGL(band_events_ols2_kernel, dim3(n_utt, (nb + kOlsBands - 1) / kOlsBands), dim3(256), lds, st, d_jobs, nb, H, d_half, d_tspec, d_zspec, d_tile_off, ctx->d_twiddle, d_flag); }
-#else
   const size_t lds = sizeof(double2) * (kOlsN / 2 + 2) + 64;
-  // one channel per workgroup while four-channel workgroups would be fewer than ~16 rounds of the chip (3 per CU): measured better at 64 and 256 utterances, worse at 1024
-  const bool single = WH_OLS_BANDS == 1 || (WH_OLS_BANDS == 0 && (int64_t)n_utt * ((nb + 3) / 4) < 16 * 3 * 256);
   {
     KernelTimer _kt(ctx, st, "band_events_kernel");
-#if WH_OLS_XCD
-#ifndef WH_OLS_GROUP
-#define WH_OLS_GROUP 4  // channels per workgroup of the large-batch form
-#endif
     const int n_xcd = n_utt >= 8 ? 8 : 1;
     const unsigned u8 = (unsigned)(((n_utt + n_xcd - 1) / n_xcd) * n_xcd);
-    if (single) hipLaunchKernelGGL(band_events_ols_kernel<1>, dim3(u8 * nb), dim3(256), lds, st, d_jobs, nb, n_utt, n_xcd, H, d_half, d_tre, d_zspec, d_tile_off, ctx->d_twiddle, d_flag);
-    else hipLaunchKernelGGL(band_events_ols_kernel<WH_OLS_GROUP>, dim3(u8 * ((nb + WH_OLS_GROUP - 1) / WH_OLS_GROUP)), dim3(256), lds, st, d_jobs, nb, n_utt, n_xcd, H, d_half, d_tre, d_zspec, d_tile_off, ctx->d_twiddle, d_flag);
-#else
-    if (single) hipLaunchKernelGGL(band_events_ols_kernel<1>, dim3(n_utt, nb), dim3(256), lds, st, d_jobs, nb, n_utt, 1, H, d_half, d_tre, d_zspec, d_tile_off, ctx->d_twiddle, d_flag);
-    else hipLaunchKernelGGL(band_events_ols_kernel<4>, dim3(n_utt, (nb + 3) / 4), dim3(256), lds, st, d_jobs, nb, n_utt, 1, H, d_half, d_tre, d_zspec, d_tile_off, ctx->d_twiddle, d_flag);
-#endif
+    hipLaunchKernelGGL(band_events_ols_kernel<1>, dim3(u8 * nb), dim3(256), lds, st, d_jobs, nb, n_utt, n_xcd, H, d_half, d_tre, d_zspec, d_tile_off, ctx->d_twiddle, d_flag);
   }
-#endif
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail("band_events_ols_kernel", e);
   return 0;

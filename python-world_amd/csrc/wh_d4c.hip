@@ -16,6 +16,7 @@
 // in registers for the whole kernel (193 VGPRs wanted where four workgroups per CU allow 128).  Re-deriving them per
 // use costs a few integer instructions.
 // (Several frames per workgroup with the three fences lifted — this one, fresh_table, stage_fence — lost: DESIGN.md §4 round 6.)
+// (a copy of its own, returning int: with the unsigned index of wh_tid.h the six d4c_kernel instances compile differently)
 __device__ __forceinline__ int wh_opaque_tid() {
   int t = threadIdx.x;
   asm volatile("" : "+v"(t));

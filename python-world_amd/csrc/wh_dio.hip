@@ -55,10 +55,7 @@ const IirCoef kDecimate[13] = {
     {2.4981398605924205, -2.1368928194784025, 0.62187513816221485, 0.0021097275904709001, 0.0063291827714127002}};
 
 constexpr int kPad = 9;       // kNFact, dio.py:452
-#ifndef WH_IIR_CHUNK
-#define WH_IIR_CHUNK 256
-#endif
-constexpr int kChunk = WH_IIR_CHUNK;  // samples of IIR output per lane (each lane also re-runs `warm` samples before its chunk)
+constexpr int kChunk = 256;  // samples of IIR output per lane (each lane also re-runs `warm` samples before its chunk)
 
 // mirror-padded input of the first pass (dio.py:458-463)
 __device__ __forceinline__ double padded(const double* __restrict__ x, int64_t n, int64_t i) {
@@ -76,10 +73,9 @@ __device__ __forceinline__ double padded(const double* __restrict__ x, int64_t n
     w0 = wt;                                                    \
   }
 
-#ifndef WH_IIR_BLOCK
-#define WH_IIR_BLOCK 32  // (16: 0.0865 + 0.0859 ms for the forward + backward pass at config 2; 32: 0.0801 + 0.0792; 64: 0.0787 + 0.0828)
-#endif
-constexpr int kIirBlock = WH_IIR_BLOCK;  // samples fetched together, a block ahead of the recurrence (wh::serial_run)
+// samples fetched together, a block ahead of the recurrence (wh::serial_run; 16: 0.0865 + 0.0859 ms for the forward +
+// backward pass at config 2; 32: 0.0801 + 0.0792; 64: 0.0787 + 0.0828)
+constexpr int kIirBlock = 32;
 
 __global__ __launch_bounds__(64) void iir_fwd_kernel(const double* __restrict__ x, const DioUtt* __restrict__ meta,
                                                      IirCoef c, int warm, double* __restrict__ tmp) {
@@ -195,10 +191,7 @@ __global__ __launch_bounds__(256) void cand_kernel(const DioUtt* __restrict__ me
 }
 
 constexpr int kMaxBands = 32;
-#ifndef WH_DIO_BAND_SEGS
-#define WH_DIO_BAND_SEGS 4
-#endif
-constexpr int kBandSegsMin = WH_DIO_BAND_SEGS;  // workgroups per (band, utterance) in the event extraction, at least
+constexpr int kBandSegsMin = 4;  // workgroups per (band, utterance) in the event extraction, at least
 constexpr int kBandSegsMax = 32;
 constexpr int kBandTilesPerSeg = 10;  // long signals: more segments, about this many 1024-sample tiles each
 
@@ -446,14 +439,11 @@ extern "C" int wh_dio(wh_ctx* ctx, void* stream, const wh_batch* b, const double
   const double fs_d = target_fs;                                           // the true ratio is ignored (Q4)
   // The band filters run on the register-tiled FIR of wh_bands.h, which wants odd tap counts (16-byte aligned input
   // pairs): an even-length filter gets one trailing zero tap (a + 0*z == a, the sums are unchanged).
-#ifndef WH_DIO_BAND_TILED
-#define WH_DIO_BAND_TILED 1
-#endif
   int max_lb = 0, taps_total = 0;
   std::vector<int32_t> tap_off(n_bands), tap_len(n_bands);
   for (int i = 0; i < n_bands; ++i) {
     if (h_band_len[i] < 1) return wh::fail_msg("wh_dio", "empty band filter");
-    tap_len[i] = WH_DIO_BAND_TILED ? (h_band_len[i] | 1) : h_band_len[i];
+    tap_len[i] = h_band_len[i] | 1;
     tap_off[i] = taps_total;
     taps_total += tap_len[i];
     if (tap_len[i] > max_lb) max_lb = tap_len[i];
@@ -587,7 +577,7 @@ extern "C" int wh_dio(wh_ctx* ctx, void* stream, const wh_batch* b, const double
     if (int rc = wh::persistent_upload(ctx, st, "dio.jobs", jobs, &d_jobs)) return rc;
   }
   if (int rc = wh::launch_band_events(ctx, st, d_jobs, n_bands, B, pad, d_taps, d_ti, d_ti + n_bands, d_ti + 2 * n_bands,
-                                      max_lb, WH_DIO_BAND_TILED != 0, ctx->d_flags + WH_FLAG_EVENT_OVERFLOW, kBandSegs))
+                                      max_lb, ctx->d_flags + WH_FLAG_EVENT_OVERFLOW, kBandSegs))
     return rc;
   // ---- candidates, sort, contour ------------------------------------------------------------------
   { wh::KernelTimer _kt(ctx, st, "cand_kernel"); hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((max_nf + 255) / 256), n_bands, B), dim3(256), 0, st, d_meta, tp, d_e,

@@ -8,12 +8,6 @@
 #include "wh_device.h"
 #include "wh_math.h"
 
-#ifndef WH_OLS_ABLATE
-#define WH_OLS_ABLATE 0  // timing experiments on the overlap-save band walker (never shipped; results differ): 1: neither the inverse
-                         // transform nor the crossing pass, 2: no crossing pass, 3: the crossing pass without its second walk
-#endif
-
-
 namespace wh {
 
 __device__ __forceinline__ unsigned long long wave_scan_incl_u64(unsigned long long v) {
@@ -32,8 +26,6 @@ __device__ __forceinline__ unsigned long long wave_scan_incl_u64(unsigned long l
 //   edge value = (1-based sample position) - v[i]/(v[i+1]-v[i])   (dio.py:201)
 // edges: [4][cap]; base_cnt[4]: running counts (block-uniform registers, updated).
 // 256 threads, tile == 1024 (4 positions per thread).  Contains barriers.
-// STRIDE: distance in doubles between consecutive samples of sig (2: one component of an interleaved complex buffer).
-template <int STRIDE = 1>
 __device__ __forceinline__ void emit_crossings(const double* sig, int64_t t0, int64_t M, int tile, double* edges,
                                                int64_t cap, int* base_cnt, unsigned long long* scratch,
                                                int32_t* overflow_flag) {
@@ -47,7 +39,7 @@ __device__ __forceinline__ void emit_crossings(const double* sig, int64_t t0, in
     if (q >= per) break;
     const int i = tid * per + q;
     const int64_t g = t0 + i;
-    const double a = sig[i * STRIDE], b = sig[(i + 1) * STRIDE], c = sig[(i + 2) * STRIDE];
+    const double a = sig[i], b = sig[i + 1], c = sig[i + 2];
     if (g + 1 < M && a * b < 0) {  // crossing of s between g and g+1
       const double fe = (double)(g + 1) - wh::fdiv(a, b - a);
       if (b < a) {
@@ -107,12 +99,12 @@ __device__ __forceinline__ void emit_crossings(const double* sig, int64_t t0, in
 // after the walk, instead of two 64-bit compares per position.  With a*b < 0 the two values differ, so ONE compare
 // tells the direction (it was two); the difference d1 of a position is d0 of the next.  All samples come in one round
 // of LDS reads (left to the compiler the walk was read - wait - test, PER / 2 times over).
-template <int STRIDE, int PER>
+template <int PER>
 __device__ __forceinline__ void crossing_flags(const double* s_ptr, int64_t left, int n_pos, unsigned* m01_out,
                                                unsigned* m23_out) {
   double s[PER + 2];
 #pragma unroll
-  for (int q = 0; q < PER + 2; ++q) s[q] = s_ptr[q * STRIDE];
+  for (int q = 0; q < PER + 2; ++q) s[q] = s_ptr[q];
   unsigned m01 = 0, m23 = 0;
   double d0 = s[1] - s[0];
 #pragma unroll
@@ -138,14 +130,14 @@ __device__ __forceinline__ void crossing_flags(const double* s_ptr, int64_t left
 // loop, the first difference's in another (a wave runs a loop as long as its busiest lane: two loops of one divide take
 // max + max rounds, one loop with both bodies took max-of-sums rounds of two).  put(train, slot, edge) stores; pos[4] are
 // the thread's first slots.  Edge = (1-based position) - v[i] / (v[i+1] - v[i])  (dio.py:201).
-template <int STRIDE, class Put>
+template <class Put>
 __device__ __forceinline__ void crossing_edges(const double* s_ptr, int64_t g_first, unsigned m01, unsigned m23, int* pos,
                                                Put put) {
   unsigned any = (m01 | (m01 >> 16)) & 0xFFFFu;
   while (any) {
     const int q = __ffs(any) - 1;
     any &= any - 1;
-    const double a = s_ptr[q * STRIDE], b = s_ptr[(q + 1) * STRIDE];
+    const double a = s_ptr[q], b = s_ptr[q + 1];
     const int t = (m01 >> q) & 1u ? 0 : 1;
     const double fe = (double)(g_first + q + 1) - wh::fdiv(a, b - a);
     put(t, pos[t], fe);
@@ -155,7 +147,7 @@ __device__ __forceinline__ void crossing_edges(const double* s_ptr, int64_t g_fi
   while (any) {
     const int q = __ffs(any) - 1;
     any &= any - 1;
-    const double a = s_ptr[q * STRIDE], b = s_ptr[(q + 1) * STRIDE], c = s_ptr[(q + 2) * STRIDE];
+    const double a = s_ptr[q], b = s_ptr[q + 1], c = s_ptr[q + 2];
     const int t = (m23 >> q) & 1u ? 2 : 3;
     const double d0 = b - a, d1 = c - b;
     const double fe = (double)(g_first + q + 1) - wh::fdiv(d0, d1 - d0);
@@ -175,7 +167,7 @@ __device__ __forceinline__ void crossing_edges(const double* s_ptr, int64_t g_fi
 // tile's search of the edge list starts, give or take the few entries the consumer allows for.  The thread whose
 // positions hold s_T knows it: its first slot plus the crossings it flagged in front of s_T.  A hint is advice: the
 // consumer clamps it into the list and checks every frame's answer against the window it staged (exact either way).
-template <int STRIDE, int PER>
+template <int PER>
 __device__ __forceinline__ void emit_crossings_block(const double* sig, int64_t t0, int64_t M, double* edges, int64_t cap,
                                                      int* base_cnt, unsigned long long* scratch,
                                                      int32_t* overflow_flag, int32_t* hint = nullptr,
@@ -185,7 +177,7 @@ __device__ __forceinline__ void emit_crossings_block(const double* sig, int64_t 
   const int tid = threadIdx.x;
   const int i0 = tid * PER;
   unsigned m01, m23;  // bits [0,16): negative-going, [16,32): positive-going
-  crossing_flags<STRIDE, PER>(sig + (int64_t)i0 * STRIDE, M - (t0 + i0), PER, &m01, &m23);
+  crossing_flags<PER>(sig + i0, M - (t0 + i0), PER, &m01, &m23);
   const unsigned long long packed = (unsigned long long)__popc(m01 & 0xFFFFu) | ((unsigned long long)__popc(m01 >> 16) << 16) |
                                     ((unsigned long long)__popc(m23 & 0xFFFFu) << 32) |
                                     ((unsigned long long)__popc(m23 >> 16) << 48);
@@ -226,14 +218,10 @@ __device__ __forceinline__ void emit_crossings_block(const double* sig, int64_t 
     }
   }
   bool over = false;
-#if WH_OLS_ABLATE == 3
-  over = m01 == 0xDEADBEEFu && m23 == m01;  // (timing experiment: the pass without its second walk)
-#else
-  crossing_edges<STRIDE>(sig + (int64_t)i0 * STRIDE, t0 + i0, m01, m23, pos, [&](int t, int at, double fe) {
+  crossing_edges(sig + i0, t0 + i0, m01, m23, pos, [&](int t, int at, double fe) {
     if (at < cap) stg(edges + (int64_t)t * cap + at, fe);
     else over = true;
   });
-#endif
   if (over) atomicOr(overflow_flag, 1);
 #pragma unroll
   for (int t = 0; t < 4; ++t) base_cnt[t] += (int)((total >> (16 * t)) & 0xFFFF);

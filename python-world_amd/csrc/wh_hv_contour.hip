@@ -1,9 +1,19 @@
 // Harvest back end: contour tracking (FixF0Contour), smoothing (SmoothF0) and the pick onto the output
-// frame grid.  Included by wh_harvest.hip inside its anonymous namespace (needs HvUtt, kRows).
+// frame grid, from the refined candidate lists and keep masks of wh_hv_refine.hip.  Built unfused.
 // Reference: world/harvest.py:301-559.  The reference walks one utterance at a time in Python; here
 // everything that is independent runs in parallel (frames, voiced sections, merge scoring) and only the
 // genuinely sequential bookkeeping (ordering/merging of a few dozen sections) is done by one lane.
-#pragma once
+#include <math.h>
+#include <hip/hip_runtime.h>
+
+#include "wh_tid.h"  // (the opaque thread index the old single Harvest unit was compiled with)
+#include "wh_device.h"
+#include "wh_host.h"
+#include "wh_hv_types.h"
+#include "wh_math.h"
+
+namespace {
+using namespace wh;
 
 struct HcUtt {  // per-utterance slices of the contour workspace (element offsets)
   int64_t f_base;    // 6 rows of nf1 doubles: base, s1, s2, s3, s4, smoothed
@@ -41,12 +51,6 @@ __device__ __forceinline__ HcList hc_list(const int64_t* __restrict__ lst, const
   l.sc = psc + (ent >> 8);
   l.n = (int)(ent & 255);
   return l;
-}
-
-inline size_t contour_workspace_bytes(int64_t f1_tot, int n_utt) {
-  // rows + runs + sections + channels, generously aligned
-  return (size_t)f1_tot * 6 * 8 + (size_t)(f1_tot + 16 * n_utt) * 2 * 4 + (size_t)(f1_tot / 2 + 16 * n_utt) * sizeof(HcSec) +
-         (size_t)(f1_tot * 32 + 1024 * n_utt) * 8 + sizeof(HcUtt) * n_utt + 4096;
 }
 
 __global__ __launch_bounds__(256) void hc_base_kernel(const HvUtt* __restrict__ meta, const HcUtt* __restrict__ hc,
@@ -577,10 +581,26 @@ __global__ __launch_bounds__(256) void hc_pick_kernel(const HvUtt* __restrict__ 
   vuv_out[m.f_off + f] = s4[idx] != 0.0 ? 1.0 : 0.0;
 }
 
-inline int harvest_contour(wh_ctx* ctx, hipStream_t st, int B, const HvUtt* d_meta, const std::vector<HvUtt>& meta,
-                           int64_t f1_tot, int64_t max_nf1, int64_t max_nf, const double* d_pf0, const double* d_psc,
-                           const int64_t* d_lst, const uint32_t* d_keep,
-                           char* d_ws, const double* tp, double* f0_out, double* vuv_out, double* dbg_f0_1ms) {
+}  // namespace
+
+namespace wh {
+
+size_t contour_workspace_bytes(int64_t f1_tot, int n_utt) {
+  // rows + runs + sections + channels, generously aligned
+  return (size_t)f1_tot * 6 * 8 + (size_t)(f1_tot + 16 * n_utt) * 2 * 4 + (size_t)(f1_tot / 2 + 16 * n_utt) * sizeof(HcSec) +
+         (size_t)(f1_tot * 32 + 1024 * n_utt) * 8 + sizeof(HcUtt) * n_utt + 4096;
+}
+
+int hv_launch_contour(wh_ctx* ctx, hipStream_t st, const HvPlan& p, const HvDev& d, const double* tp, double* f0_out,
+                      double* vuv_out, double* dbg_f0_1ms) {
+  const int B = p.B;
+  const std::vector<HvUtt>& meta = p.meta;
+  const HvUtt* d_meta = d.meta;
+  const int64_t f1_tot = p.f1_tot, max_nf1 = p.max_nf1, max_nf = p.max_nf;
+  const double *d_pf0 = d.rf0, *d_psc = d.rsc;
+  const int64_t* d_lst = d.lst;
+  const uint32_t* d_keep = d.keep;
+  char* d_ws = d.ct;
   auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
   std::vector<HcUtt> hc(B);
   int64_t run_tot = 0, sec_tot = 0, ch_tot = 0, max_secs = 0;
@@ -610,21 +630,21 @@ inline int harvest_contour(wh_ctx* ctx, hipStream_t st, int B, const HvUtt* d_me
   HcSec* d_secs = reinterpret_cast<HcSec*>(d_ws + o_secs);
   int32_t* d_ns = reinterpret_cast<int32_t*>(d_ws + o_ns);
   double* d_ch = reinterpret_cast<double*>(d_ws + o_ch);
-  if (int rc = wh::persistent_upload(ctx, st, "hv.contour", hc, &d_hc)) return rc;
+  if (int rc = persistent_upload(ctx, st, "hv.contour", hc, &d_hc)) return rc;
   const dim3 gf((unsigned)((max_nf1 + 255) / 256), B);
-  { wh::KernelTimer _kt(ctx, st, "hc_base_kernel"); hipLaunchKernelGGL(hc_base_kernel, gf, dim3(256), 0, st, d_meta, d_hc, d_pf0, d_psc, d_lst, d_keep, d_rows); }
+  { KernelTimer _kt(ctx, st, "hc_base_kernel"); hipLaunchKernelGGL(hc_base_kernel, gf, dim3(256), 0, st, d_meta, d_hc, d_pf0, d_psc, d_lst, d_keep, d_rows); }
   WH_LAUNCH_CHECK("hc_base_kernel");
-  { wh::KernelTimer _kt(ctx, st, "hc_step1_kernel"); hipLaunchKernelGGL(hc_step1_kernel, gf, dim3(256), 0, st, d_meta, d_hc, d_rows); }
+  { KernelTimer _kt(ctx, st, "hc_step1_kernel"); hipLaunchKernelGGL(hc_step1_kernel, gf, dim3(256), 0, st, d_meta, d_hc, d_rows); }
   WH_LAUNCH_CHECK("hc_step1_kernel");
-  { wh::KernelTimer _kt(ctx, st, "hc_sections_kernel"); hipLaunchKernelGGL(hc_sections_kernel, dim3(B), dim3(256), 0, st, d_meta, d_hc, d_rows, d_runs, d_secs, d_ns); }
+  { KernelTimer _kt(ctx, st, "hc_sections_kernel"); hipLaunchKernelGGL(hc_sections_kernel, dim3(B), dim3(256), 0, st, d_meta, d_hc, d_rows, d_runs, d_secs, d_ns); }
   WH_LAUNCH_CHECK("hc_sections_kernel");
-  { wh::KernelTimer _kt(ctx, st, "hc_extend_kernel"); hipLaunchKernelGGL(hc_extend_kernel, dim3((unsigned)max_secs, B), dim3(64), 0, st, d_meta, d_hc, d_rows, d_pf0, d_lst, d_keep, d_secs, d_ns, d_ch); }
+  { KernelTimer _kt(ctx, st, "hc_extend_kernel"); hipLaunchKernelGGL(hc_extend_kernel, dim3((unsigned)max_secs, B), dim3(64), 0, st, d_meta, d_hc, d_rows, d_pf0, d_lst, d_keep, d_secs, d_ns, d_ch); }
   WH_LAUNCH_CHECK("hc_extend_kernel");
-  { wh::KernelTimer _kt(ctx, st, "hc_merge_kernel"); hipLaunchKernelGGL(hc_merge_kernel, dim3(B), dim3(256), 0, st, d_meta, d_hc, d_rows, d_pf0, d_psc, d_lst, d_keep, d_secs, d_ns, d_ch, d_runs); }
+  { KernelTimer _kt(ctx, st, "hc_merge_kernel"); hipLaunchKernelGGL(hc_merge_kernel, dim3(B), dim3(256), 0, st, d_meta, d_hc, d_rows, d_pf0, d_psc, d_lst, d_keep, d_secs, d_ns, d_ch, d_runs); }
   WH_LAUNCH_CHECK("hc_merge_kernel");
-  { wh::KernelTimer _kt(ctx, st, "hc_smooth_kernel"); hipLaunchKernelGGL(hc_smooth_kernel, dim3(B), dim3(256), 0, st, d_meta, d_hc, d_rows, d_runs, d_ch); }
+  { KernelTimer _kt(ctx, st, "hc_smooth_kernel"); hipLaunchKernelGGL(hc_smooth_kernel, dim3(B), dim3(256), 0, st, d_meta, d_hc, d_rows, d_runs, d_ch); }
   WH_LAUNCH_CHECK("hc_smooth_kernel");
-  { wh::KernelTimer _kt(ctx, st, "hc_pick_kernel"); hipLaunchKernelGGL(hc_pick_kernel, dim3((unsigned)((max_nf + 255) / 256), B), dim3(256), 0, st, d_meta, d_hc, d_rows, tp, f0_out, vuv_out); }
+  { KernelTimer _kt(ctx, st, "hc_pick_kernel"); hipLaunchKernelGGL(hc_pick_kernel, dim3((unsigned)((max_nf + 255) / 256), B), dim3(256), 0, st, d_meta, d_hc, d_rows, tp, f0_out, vuv_out); }
   WH_LAUNCH_CHECK("hc_pick_kernel");
   if (dbg_f0_1ms) {
     for (int u = 0; u < B; ++u)
@@ -633,3 +653,5 @@ inline int harvest_contour(wh_ctx* ctx, hipStream_t st, int B, const HvUtt* d_me
   }
   return 0;
 }
+
+}  // namespace wh

@@ -4,13 +4,7 @@
 // ================================================================================================
 #include "wh_host.h"
 #include "wh_math.h"
-// (the opaque thread index of the spectral units: wh_synthesis.hip)
-__device__ __forceinline__ unsigned wh_opaque_tid() {
-  unsigned t = threadIdx.x;
-  asm volatile("" : "+v"(t));
-  return t;
-}
-#define WH_TID wh_opaque_tid()
+#include "wh_tid.h"  // (the opaque thread index of the spectral units)
 #include "wh_device.h"
 #include "wh_syn_types.h"
 #include "wh_minphase.h"

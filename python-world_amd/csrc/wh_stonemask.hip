@@ -171,7 +171,7 @@ __global__ __launch_bounds__(64) void stonemask_kernel(
 // PICK floor(index_raw_j) depends on the frame and is evaluated per tap exactly as the reference does (the
 // quantisation moves picks by up to a sample at 16 kHz).  Nothing is staged: eight lanes per frame accumulate the 2,
 // then the 6, harmonic bins straight from global memory with LDS twiddles — the shape of hv_refine_row's tabulated
-// path (wh_harvest.hip), where the per-wave-pass set-up and cross-lane sums are shared by 8 frames instead of being
+// path (wh_hv_refine.hip), where the per-wave-pass set-up and cross-lane sums are shared by 8 frames instead of being
 // paid per frame by a whole wave (32 wave-wide reductions per frame were half of the staged kernel's instructions).
 // Frames the table does not cover (windows reaching before the signal start, where the reference's rounding changes
 // sign, or f0 below the table's floor) are flagged in `todo` and taken by stonemask_kernel in a second launch.

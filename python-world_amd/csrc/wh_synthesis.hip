@@ -8,16 +8,11 @@
 //                     y with the reference's clipped-index semantics.
 #include "wh_host.h"
 #include "wh_math.h"
-// response_kernel walks a run of pulses in a loop.  With the plain thread index every per-thread LDS / twiddle address
-// of the ~15 transform passes in the loop body is a loop invariant: LLVM hoists them all in front of the loop and keeps
-// them alive across it (248 VGPRs, 2 waves per SIMD).  Reading the index through an empty volatile asm makes each use
-// its own value; the few integer instructions that are recomputed cost nothing next to 128 spare registers.
-__device__ __forceinline__ unsigned wh_opaque_tid() {
-  unsigned t = threadIdx.x;
-  asm volatile("" : "+v"(t));
-  return t;
-}
-#define WH_TID wh_opaque_tid()
+// response_kernel walks a run of pulses in a loop and reads the thread index opaquely (wh_tid.h): with the plain index
+// every per-thread LDS / twiddle address of the ~15 transform passes in the loop body is hoisted in front of the loop and
+// kept alive across it (248 VGPRs, 2 waves per SIMD); the few integer instructions that are recomputed cost nothing
+// next to 128 spare registers.
+#include "wh_tid.h"
 #include "wh_device.h"
 #include "wh_syn_types.h"
 #include "wh_minphase.h"

@@ -65,8 +65,7 @@ def test_restated_radix_plan():
 # each other, and the probe are left out)
 CALL_SITES = {
     ("wh_api.hip", "fft_lds_wave"): 2,
-    ("wh_bands.h", "fft_lds"): 2,
-    ("wh_bands.h", "irfft_lds"): 1,  # (under a preprocessor branch that is not compiled)
+    ("wh_bands.h", "fft_lds"): 1,
     ("wh_bands.h", "rfft_lds"): 3,
     ("wh_cheaptrick.hip", "fft_lds"): 3,
     ("wh_cheaptrick.hip", "rfft_lds"): 1,

@@ -190,7 +190,7 @@ def test_refinement_windows_do_not_depend_on_the_frame_time():
             common = math.pi * ((idx_raw - 1) / fs_d - t0) / (ln / fs_d)
             ref = 0.42 + 0.5 * np.cos(2 * common) + 0.08 * np.cos(4 * common)
             j = np.arange(ln)
-            c = np.cos(math.pi * (2 * ((j - h + (0.001 + 0.5) - 1.0) / fs_d) / (ln / fs_d)))   # wh_harvest.hip, host table
+            c = np.cos(math.pi * (2 * ((j - h + (0.001 + 0.5) - 1.0) / fs_d) / (ln / fs_d)))   # wh_hv_refine.hip, host table
             tab = 0.42 + 0.5 * c + 0.08 * (2 * c * c - 1)
             assert np.max(np.abs(tab - ref)) < 5e-12 * max(1.0, t0)   # the cancellation noise of the reference itself (measured: 3e-13 * t0)
     # StoneMask: wt = (index_raw - 1)/fs - t0 with index_raw = half_up((t0 + bt)*fs), bt the 4-decimal quantised times

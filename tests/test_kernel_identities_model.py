@@ -1,7 +1,7 @@
 """CPU models of the three rewrites of round 4 that replaced a kernel's arithmetic by a cheaper equivalent, each checked
 in NumPy against the form the reference computes (no GPU involved; the GPU suite checks the kernels end to end):
 
-  * hv_refine_row (wh_harvest.hip): the two windowed spectra of GetRefinedF0 (world/harvest.py:169-211) at the harmonic
+  * hv_refine_row (wh_hv_refine.hip): the two windowed spectra of GetRefinedF0 (world/harvest.py:169-211) at the harmonic
     bins as sums over sample PAIRS about the window centre.  What the refinement reads of them — |X|^2 and
     Re(X) Im(D) - Im(X) Re(D) — does not see the common unit factor that referring the phase to the centre introduces.
   * band_taps_fft_kernel / band_events_ols_kernel (wh_bands.h): a Harvest band filter (harvest.py:253-256) is symmetric
@@ -74,7 +74,7 @@ def test_pair_sums_about_the_window_centre_give_the_refinements_invariants(f0c):
 
 
 def test_packed_refinement_geometry_round_trips():
-    """refine_pack / refine_unpack (wh_harvest.hip): half length, first bin against a base that follows from the half
+    """refine_pack / refine_unpack (wh_hv_refine.hip): half length, first bin against a base that follows from the half
     length, harmonic count, the other bins as offsets from multiples of the first — 28 bits — for every candidate value a
     Harvest refinement can meet at the decimated rates in use."""
     for fs_d in (8000.0, 7350.0, 8820.0):

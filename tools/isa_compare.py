@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Device assembly of two source trees, function by function: did a change move a kernel?
 
-    tools/isa_compare.py <old tree> <new tree> [--work DIR] unit [unit ...]
+    tools/isa_compare.py <old tree> <new tree> [--work DIR] [--gone NAME ...] unit [unit ...]
 
 e.g.  git worktree add /tmp/parent HEAD^ && tools/isa_compare.py /tmp/parent . wh_d4c wh_cheaptrick wh_synthesis wh_timebase
 
@@ -11,7 +11,10 @@ that was not inlined), and what depends only on a function's position in its fil
 .LBB / .Ltmp / .Lfunc labels, `;` comments, blank and debug lines.  Functions are matched across units by demangled name
 (without namespaces: a kernel may have changed files, a type its namespace).  The kernel descriptor is part of a kernel's
 text.  Per function: identical, or the first differing line and both sides' registers, LDS, scratch and instruction count.
-Needs hipcc, no GPU.  Exit status 1 if any function differs or exists on one side only."""
+--gone NAME (repeatable) declares a function of the old tree — its short demangled name as this tool prints it — as removed
+on purpose: it is listed under a heading of its own and does not count against the run.
+Needs hipcc, no GPU.  Exit status 1 if any function differs, exists on one side only without having been declared gone, or
+was declared gone and is not (or was never there)."""
 import importlib.util
 import os
 import re
@@ -102,6 +105,11 @@ def main():
         i = args.index("--work")
         work = args[i + 1]
         del args[i:i + 2]
+    gone = []
+    while "--gone" in args:
+        i = args.index("--gone")
+        gone.append(args[i + 1])
+        del args[i:i + 2]
     if len(args) < 3:
         sys.exit(__doc__)
     old, new, units = os.path.abspath(args[0]), os.path.abspath(args[1]), args[2:]
@@ -117,7 +125,18 @@ def main():
     a, b = sides
     bad = 0
     print("units: %s" % " ".join(units))
+    removed = [n for n in gone if n in a and n not in b]
+    if gone:
+        print("declared removed (%d):" % len(gone))
+        for n in gone:
+            if n in removed:
+                print("gone       %s  (%s; %s)" % (n, a[n]["unit"], describe(a[n])))
+            else:
+                bad += 1
+                print("NOT GONE   %s  (%s)" % (n, "still in the new tree" if n in b else "not in the old tree"))
     for name in sorted(set(a) | set(b)):
+        if name in removed:
+            continue
         if name not in a or name not in b:
             bad += 1
             print("ONLY %s  %s  (%s)" % ("old" if name in a else "new", name, (a.get(name) or b.get(name))["unit"]))
@@ -133,7 +152,8 @@ def main():
         print("    old: %s\n    new: %s" % (describe(ra), describe(rb)))
         print("    first difference at normalised line %d:\n      old: %s\n      new: %s" % (
             i, ra["text"][i].strip() if i < len(ra["text"]) else "<end>", rb["text"][i].strip() if i < len(rb["text"]) else "<end>"))
-    print("%d functions, %d identical, %d not" % (len(set(a) | set(b)), len(set(a) | set(b)) - bad, bad))
+    total = len((set(a) | set(b)) - set(removed))
+    print("%d functions, %d identical, %d not; %d removed as declared" % (total, total - bad, bad, len(removed)))
     return 1 if bad else 0
 
 
