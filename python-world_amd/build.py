@@ -37,6 +37,7 @@ TU_FLAGS = {
     "wh_d4c.hip": ["-ffp-contract=fast-honor-pragmas"],
     "wh_cheaptrick.hip": ["-ffp-contract=fast-honor-pragmas"],
     "wh_fft_probe.hip": ["-ffp-contract=fast-honor-pragmas"],  # (a test hook: the transforms as most of their callers compile them)
+    "wh_spectral_probe.hip": ["-ffp-contract=fast-honor-pragmas"],  # (a test hook: wh_spectral.h as wh_cheaptrick.hip compiles it)
 }
 
 

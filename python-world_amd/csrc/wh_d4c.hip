@@ -497,10 +497,10 @@ __global__ __launch_bounds__(ft_love(NLT)) void love_train_kernel(
 // Sum of the m smallest of K non-negative values and their total, without sorting and without LDS atomics.
 // The reference sorts the K powers and prefix-sums them (world/d4c.py:206-208); only the VALUES of the m smallest
 // enter the sum, and m = K - (boundary + 1) is close to K, so the kernel finds the few LARGE values to leave out:
-//   (1) per wave, the maximum IEEE exponent (shuffles) and the population counts of the 8 exponents at and below it
-//       by ballot (scalar unit); counts AND the wave's maximum go through LDS together, so one hop yields the block
-//       maximum and the block's counts; the window slides further down in the rare case that the K - m largest span
-//       more than 8 octaves;
+//   (1) per wave, the maximum IEEE exponent (shuffles) and the population counts of the WIN = 1 << WH_D4C_SEL_DB = 4
+//       exponents at and below it (packed counters summed by DPP); counts AND the wave's maximum go through LDS
+//       together, so one hop yields the block maximum and the block's counts; the window slides further down, WIN
+//       exponents per round, while the K - m largest span more than that;
 //   (2) the one exponent bin that holds the threshold is compacted into a list at offsets derived from the same
 //       ballots (no atomic counter) and its members are ranked against each other (~11 on speech); equal values are
 //       interchangeable in a sum, so ties need no index rule.
@@ -546,11 +546,12 @@ template <int K, int FT, int PER>
 __device__ __forceinline__ void sum_smallest(const double (&x)[PER], unsigned valid, int m, wh::ckp<double> work, wh::ckp<double> scratch,
                                              double* s_small, double* s_total) {
   constexpr int NW = FT / 64;
-  // exponents per round.  On speech the K - m (~22) largest bins lie within 4 octaves of the maximum on average, 7 at
-  // most (measured on the oracle's spectra): one round of 8 almost always; the loop below slides on otherwise.
+  // exponents per round: WIN = 1 << DB, 4 as built.  On speech the K - m (~22) largest bins lie within 4 octaves of the
+  // maximum on average, 7 at most (measured on the oracle's spectra), so a second round is nothing unusual; the loop
+  // below slides on as far as the values reach (tests/test_hip_d4c_select.py: ten rounds).
   // Long spectra (K = 2049 at 48 kHz: 65 bins dropped, spread over more octaves, hundreds of values in the threshold bin)
-  // take 16 exponents per round and 4 mantissa bits per refinement level: the same number of ballots in half as many
-  // rounds, i.e. half as many barrier pairs and count exchanges.
+  // have a DB of their own, WH_D4C_SEL_DB_LONG: more exponents per round and mantissa bits per refinement level mean
+  // fewer rounds, barrier pairs and count exchanges for more counters per round.  Both are 2 as built.
 #ifndef WH_D4C_SEL_DB_LONG
 #define WH_D4C_SEL_DB_LONG 2
 #endif
@@ -604,8 +605,8 @@ __device__ __forceinline__ void sum_smallest(const double (&x)[PER], unsigned va
 #pragma unroll
       for (int i = 0; i < NW; ++i) gtop = cnts[i * (WIN + 1) + WIN] > gtop ? cnts[i * (WIN + 1) + WIN] : gtop;
     }
-    // lane e sums the waves' counts of offset e (and what the waves in front of this one hold of it); the eight results
-    // come back through readlane as uniform values — 8 LDS reads in 8 lanes instead of 64 in every lane
+    // lane e sums the waves' counts of offset e (and what the waves in front of this one hold of it); the WIN results
+    // come back through readlane as uniform values — WIN LDS reads per wave in WIN lanes instead of in every lane
     int tot_l = 0, bef_l = 0;
     if (lane < WIN) {
 #pragma unroll
@@ -643,7 +644,7 @@ __device__ __forceinline__ void sum_smallest(const double (&x)[PER], unsigned va
   // The members of the threshold bin are ranked against each other below, in_bin^2 / FT comparisons: fine for the ~11
   // members a 2048-point band spectrum leaves there (22 bins dropped of 1025), not for the hundreds of a 4096-point one
   // (65 of 2049: 41 % of the whole kernel at 48 kHz).  While the bin holds more than 32 values it is split by the next
-  // three mantissa bits — the same ballot counts, eight digits, one LDS hop — and only the digit that holds the
+  // DB mantissa bits — the same packed counts, WIN digits, one LDS hop — and only the digit that holds the
   // threshold stays a candidate: larger digits are dropped whole, smaller ones kept whole.
   unsigned cand = 0;  // bit q: slot q is a member of the current threshold set
 #pragma unroll
@@ -1366,4 +1367,160 @@ extern "C" int wh_aperiodicity_gate(wh_ctx* ctx, void* stream, int64_t n_frames,
   { wh::KernelTimer _kt(ctx, st, "ap_gate_kernel"); hipLaunchKernelGGL(ap_gate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, aperiodicity, gate, (long long)n_frames, k_bins); }
   WH_LAUNCH_CHECK("ap_gate_kernel");
   return 0;
+}
+
+// ---- test hooks: sum_smallest and the run-resident helpers on caller data (tests/test_hip_d4c_select.py,
+// tests/test_hip_spectral_helpers.py).  Nothing in the library calls them.  One workgroup of ft_of(N) threads per row, the
+// LDS block laid out as d4c_frame lays it out (2N doubles of transform buffer: work area / low-band scratch / mirrored
+// spectrum; 40 doubles of reduction scratch), the helpers instantiated with d4c_frame's own template arguments.
+namespace {
+
+template <int N>
+__global__ __launch_bounds__(ft_of(N)) void d4c_select_probe_kernel(const double* __restrict__ vals_, double* __restrict__ out_,
+                                                                    int layout, int m, long long count) {
+  constexpr int FT = Runs<N>::FT, K = Runs<N>::K;
+  constexpr int MB = N / 2;
+  constexpr int PJ = (MB / 2 + 1 + FT - 1) / FT;  // pair jobs per thread, as in the band stage
+  static_assert((K + FT - 1) / FT <= 2 * PJ, "layout 1 needs ceil(K / FT) slots");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const wh::ckp<double> lds_all = wh::ck_make(reinterpret_cast<double*>(smem), 2 * N + 40, wh::WH_CK_LDS_OTHER);
+  const wh::ckp<double> zr = wh::ck_sub(lds_all, 0, 2 * N, wh::WH_CK_LDS_MAIN);
+  const wh::ckp<double> scratch = wh::ck_sub(lds_all, 2 * N, 40, wh::WH_CK_LDS_SCRATCH);
+  const long long c = blockIdx.x;
+  if (c >= count) return;
+  const wh::ckp<const double> v = wh::ck_make(vals_ + c * K, K, wh::WH_CK_IN);
+  const wh::ckp<double> o = wh::ck_make(out_ + 2 * c, 2, wh::WH_CK_OUT);
+  double px[2 * PJ];
+  unsigned pvalid = 0;
+#pragma unroll
+  for (int q = 0; q < 2 * PJ; ++q) px[q] = 0.0;
+  if (layout == 0) {
+    // the band stage's own assignment: job i of thread t holds the bins t + i FT and N/2 - (t + i FT)
+#pragma unroll
+    for (int i = 0; i < PJ; ++i) {
+      const int k = threadIdx.x + i * FT;
+      if (k <= MB / 2) {
+        px[2 * i] = v[k];
+        pvalid |= 1u << (2 * i);
+        if (k != MB - k) {  // (the middle bin pairs with itself; k = 0 pairs with N/2)
+          px[2 * i + 1] = v[MB - k];
+          pvalid |= 2u << (2 * i);
+        }
+      }
+    }
+  } else {
+    // bin k on thread (K - 1 - k) % FT, slots filled in the order of k
+    const int kfirst = (K - 1 - (int)threadIdx.x) % FT;
+#pragma unroll
+    for (int q = 0; q < 2 * PJ; ++q) {
+      const int k = kfirst + q * FT;
+      if (k < K) {
+        px[q] = v[k];
+        pvalid |= 1u << q;
+      }
+    }
+  }
+  double s_small, s_total;
+  sum_smallest<K, FT, 2 * PJ>(px, pvalid, m, zr, scratch, &s_small, &s_total);
+  if (threadIdx.x == 0) {
+    o[0] = s_small;
+    o[1] = s_total;
+  }
+}
+
+// which 0: low_band_replica_runs(p, fs, f0[c], rh[c]) -> p;  1: fill_mirrored_runs(p), BandWindow(half = rh[c]) -> band
+template <int N>
+__global__ __launch_bounds__(ft_of(N)) void d4c_runs_probe_kernel(const double* __restrict__ in_, double* __restrict__ out_,
+                                                                  const double* __restrict__ f0_, const double* __restrict__ rh_,
+                                                                  int which, double fs, long long count) {
+  constexpr int K = Runs<N>::K, KR = Runs<N>::KR;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const wh::ckp<double> lds_all = wh::ck_make(reinterpret_cast<double*>(smem), 2 * N + 40, wh::WH_CK_LDS_OTHER);
+  const wh::ckp<double> zr = wh::ck_sub(lds_all, 0, 2 * N, wh::WH_CK_LDS_MAIN);
+  const long long c = blockIdx.x;
+  if (c >= count) return;
+  const wh::ckp<const double> in = wh::ck_make(in_ + c * K, K, wh::WH_CK_IN);
+  const wh::ckp<double> o = wh::ck_make(out_ + c * K, K, wh::WH_CK_OUT);
+  const int k0 = threadIdx.x * KR;
+  double p[KR], res[KR];
+#pragma unroll
+  for (int r = 0; r < KR; ++r) p[r] = k0 + r < K ? in[k0 + r] : 0.0;
+  const double rh = rh_[c];
+  if (which == 0) {
+    low_band_replica_runs<N>(p, zr, fs, f0_[c], rh);
+#pragma unroll
+    for (int r = 0; r < KR; ++r) res[r] = p[r];
+  } else {
+#pragma unroll
+    for (int r = 0; r < KR; ++r) res[r] = 0.0;
+    fill_mirrored_runs<N>(p, zr, fs);
+    // (a half-width outside [0, fs] is not a smoothing anyone runs, and its window would be walked bin by bin)
+    if (rh >= 0.0 && rh <= fs) {
+      wh::BandWindow bw;
+      bw.init(zr, N, fs, rh);
+      bw.run<KR>(k0, K, res);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < KR; ++r)
+    if (k0 + r < K) o[k0 + r] = res[r];
+}
+
+template <int N>
+int launch_select_probe(hipStream_t st, int layout, int m, const double* vals, double* out, long long count) {
+  const size_t lds = sizeof(double) * (2 * N + 40);
+  if (int rc = wh::allow_lds(&d4c_select_probe_kernel<N>, lds)) return rc;
+  hipLaunchKernelGGL(d4c_select_probe_kernel<N>, dim3((unsigned)count), dim3(ft_of(N)), lds, st, vals, out, layout, m, count);
+  WH_LAUNCH_CHECK("d4c_select_probe_kernel");
+  return 0;
+}
+
+template <int N>
+int launch_runs_probe(hipStream_t st, int which, double fs, const double* f0, const double* rh, const double* in, double* out,
+                      long long count) {
+  const size_t lds = sizeof(double) * (2 * N + 40);
+  if (int rc = wh::allow_lds(&d4c_runs_probe_kernel<N>, lds)) return rc;
+  hipLaunchKernelGGL(d4c_runs_probe_kernel<N>, dim3((unsigned)count), dim3(ft_of(N)), lds, st, in, out, f0, rh, which, fs, count);
+  WH_LAUNCH_CHECK("d4c_runs_probe_kernel");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int wh_d4c_select_probe(wh_ctx* ctx, void* stream, int n, int layout, int m, const double* vals, double* out,
+                                   int64_t count) {
+  if (!ctx || !vals || !out || count < 0 || count > 0x7fffffffLL || (layout != 0 && layout != 1))
+    return wh::fail_msg("wh_d4c_select_probe", "bad argument");
+  if (n != 512 && n != 1024 && n != 2048 && n != 4096 && n != 8192)
+    return wh::fail_msg("wh_d4c_select_probe", "n must be one of D4C's transform lengths 512 ... 8192");
+  if (m < 1 || m > n / 2) return wh::fail_msg("wh_d4c_select_probe", "m must lie in [1, K - 1] (at least one value is left out)");
+  WH_ENTER(ctx);
+  if (count == 0) return 0;
+  const hipStream_t st = (hipStream_t)stream;
+  switch (n) {
+    case 512: return launch_select_probe<512>(st, layout, m, vals, out, (long long)count);
+    case 1024: return launch_select_probe<1024>(st, layout, m, vals, out, (long long)count);
+    case 2048: return launch_select_probe<2048>(st, layout, m, vals, out, (long long)count);
+    case 4096: return launch_select_probe<4096>(st, layout, m, vals, out, (long long)count);
+    default: return launch_select_probe<8192>(st, layout, m, vals, out, (long long)count);
+  }
+}
+
+extern "C" int wh_d4c_runs_probe(wh_ctx* ctx, void* stream, int n, int which, double fs, const double* f0,
+                                 const double* reach_or_half, const double* in, double* out, int64_t count) {
+  if (!ctx || !reach_or_half || !in || !out || count < 0 || count > 0x7fffffffLL || (which != 0 && which != 1) ||
+      (which == 0 && !f0) || !(fs > 0))
+    return wh::fail_msg("wh_d4c_runs_probe", "bad argument");
+  if (n != 512 && n != 1024 && n != 2048 && n != 4096 && n != 8192)
+    return wh::fail_msg("wh_d4c_runs_probe", "n must be one of D4C's transform lengths 512 ... 8192");
+  WH_ENTER(ctx);
+  if (count == 0) return 0;
+  const hipStream_t st = (hipStream_t)stream;
+  switch (n) {
+    case 512: return launch_runs_probe<512>(st, which, fs, f0, reach_or_half, in, out, (long long)count);
+    case 1024: return launch_runs_probe<1024>(st, which, fs, f0, reach_or_half, in, out, (long long)count);
+    case 2048: return launch_runs_probe<2048>(st, which, fs, f0, reach_or_half, in, out, (long long)count);
+    case 4096: return launch_runs_probe<4096>(st, which, fs, f0, reach_or_half, in, out, (long long)count);
+    default: return launch_runs_probe<8192>(st, which, fs, f0, reach_or_half, in, out, (long long)count);
+  }
 }

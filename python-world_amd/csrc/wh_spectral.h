@@ -72,7 +72,13 @@ __device__ __forceinline__ void low_band_replica(ckp<double> p, ckp<double> tmp,
 // offsets, constant per frame): a plain windowed sum.  Each thread owns a run of consecutive bins and slides the
 // window along it (two LDS reads per further bin), so the smoothing needs the mirrored spectrum in LDS and ONE
 // barrier — not a 2048-element block prefix sum (four barriers and a shuffle scan) plus four interpolated
-// look-ups per bin; and it is free of the cancellation of differencing two large cumulative values.
+// look-ups per bin; and the first bin of a run is free of the cancellation of differencing two large cumulative values.
+// The further bins of a run are not free of all of it: s += v[hi] - v[lo] keeps the rounding of every sum it has held, so a
+// bin that enters and leaves the window inside a run leaves up to 2^-53 of its OWN size in s for the rest of the run (runs
+// are 2 to 9 bins).  The error of bin r of a run is at most (W + 2 r + 6) 2^-53 times the sum of |v| over what the run has
+// touched (tests/_spectral_reference.py derives it, tests/test_hip_spectral_helpers.py holds both forms to it); relative to
+// the output that is rounding level on spectra whose neighbouring bins are of one order of magnitude, and 2^-53 times the
+// ratio where a bin towers over the window that has just left it (DESIGN.md section 2 quotes the measured figures).
 template <int NT, int N>
 __device__ __forceinline__ void fill_mirrored(ckp<const double> p_half, ckp<double> v, double fs) {
   const double df = fs / N;

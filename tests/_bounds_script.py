@@ -139,6 +139,43 @@ def main():
         probe["-".join(str(v) for v in shape)] = {"rc": rc, "flag": fl[_hip.FLAG_OOB], "record": list(_hip.bounds_last()),
                                                   "finite": bool(np.all(np.isfinite(y_d.cpu().numpy())))}
     out["fft_probe"] = probe
+    # ---- the selection probe and the two spectral probes (csrc/wh_d4c.hip, csrc/wh_spectral_probe.hip): one call per shape —
+    # exponents over 39 octaves (every selection round) and all values equal (every refinement level, the whole row in the
+    # ranked list); the replica with f0 around fs / 2 (every bin a node, the mirror branch of the LDS form) -----------------
+    def taken(rc, y_d):
+        fl = rt.take_flags()
+        return {"rc": rc, "flag": fl[_hip.FLAG_OOB], "record": list(_hip.bounds_last()),
+                "finite": bool(np.all(np.isfinite(y_d.cpu().numpy())))}
+
+    d4c_ft = {512: 256, 1024: 128, 2048: 256, 4096: 512, 8192: 512}
+    sel = {}
+    for n in sorted(d4c_ft):
+        k = n // 2 + 1
+        rng = np.random.RandomState(n)
+        rows = np.concatenate([np.floor(2.0 ** rng.uniform(0.0, 39.0, (8, k))), np.full((2, k), 3.0)])
+        x_d, y_d = rt.to_device(rows.reshape(-1)), rt.empty((2 * len(rows),))
+        for layout in (0, 1):
+            rc = rt.lib.wh_d4c_select_probe(rt.ctx, rt.stream(), n, layout, k - 22, rt.ptr(x_d), rt.ptr(y_d), len(rows))
+            sel["%d-%d" % (n, layout)] = taken(rc, y_d)
+    out["select_probe"] = sel
+    spectral = {}
+    for form, n, ft, fs in [("lds", 256, 128, 8000), ("lds", 512, 128, 16000), ("lds", 1024, 128, 16000), ("lds", 2048, 256, 48000),
+                            ("lds", 4096, 256, 96000)] + [("runs", n, d4c_ft[n], 16000 if n <= 2048 else 12000 * (n // 1024))
+                                                          for n in sorted(d4c_ft)]:
+        k, df = n // 2 + 1, fs / n
+        f0 = np.array([fs / 2 - 0.5 * df, fs / 2 - 0.5 * df, fs / 2 + 0.5 * df, fs / 2 + 0.5 * df, 0.75 * fs, 150.0])
+        reach = np.array([f0[0] + df, 1.2 * f0[1], f0[2] + df, 1.2 * f0[3], 1.2 * f0[4], 1.2 * f0[5]])
+        x_d = rt.to_device(np.random.RandomState(n).uniform(0.5, 1.5, len(f0) * k))
+        f0_d, reach_d, y_d = rt.to_device(f0), rt.to_device(reach), rt.empty((len(f0) * k,))
+        for which, rh_d in ((0, reach_d), (1, rt.to_device(f0 / 3))):
+            if form == "lds":
+                rc = rt.lib.wh_spectral_probe(rt.ctx, rt.stream(), n, ft, which, float(fs), rt.ptr(f0_d), rt.ptr(rh_d), rt.ptr(x_d),
+                                              rt.ptr(y_d), len(f0))
+            else:
+                rc = rt.lib.wh_d4c_runs_probe(rt.ctx, rt.stream(), n, which, float(fs), rt.ptr(f0_d), rt.ptr(rh_d), rt.ptr(x_d),
+                                              rt.ptr(y_d), len(f0))
+            spectral["%s-%d-%d" % (form, n, which)] = taken(rc, y_d)
+    out["spectral_probes"] = spectral
     print("BOUNDS_JSON " + json.dumps(out))
 
 

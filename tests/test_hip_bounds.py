@@ -11,7 +11,9 @@ expects: the positive control fires with the right record; the CheapTrick fixtur
 records; an f0 sweep from 1 Hz to 1.5 fs at five (rate, transform) pairs — caller-supplied contours the reference's
 estimators never return (world/cheaptrick.py:64-131 takes any f0) — stays inside every buffer; config 2 at its full
 size, a Harvest + Requiem batch and a 48 kHz utterance run clean; the transform probe (csrc/wh_fft_probe.hip), one launch
-each of a handful of shapes, stays inside its LDS buffers and the twiddle block."""
+each of a handful of shapes, stays inside its LDS buffers and the twiddle block; the selection probe and the two spectral
+probes (csrc/wh_d4c.hip, csrc/wh_spectral_probe.hip), one call per shape on the inputs that reach furthest — every selection
+round and refinement level, the replica with every bin a node — stay inside theirs."""
 import json
 import os
 import subprocess
@@ -24,7 +26,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 BOUNDS_TUS = ("wh_api", "wh_cheaptrick", "wh_stonemask", "wh_harvest", "wh_hv_front", "wh_hv_refine", "wh_hv_contour", "wh_timebase", "wh_synthesis", "wh_requiem", "wh_d4c",
-              "wh_fft_probe")
+              "wh_fft_probe", "wh_spectral_probe")
 VARIANT = os.path.join(ROOT, "python-world_amd", "lib", "variants", "libworld_hip_bounds.so")
 
 
@@ -90,6 +92,22 @@ def test_transform_probe_stays_inside_its_buffers(report):
     # irfft_lds; 37 transforms each (a half-filled last workgroup where two share one)
     assert len(report["fft_probe"]) == 6
     for shape, r in report["fft_probe"].items():
+        assert r["rc"] == 0 and r["flag"] == 0 and r["record"] == [0, 0, 0, 0] and r["finite"], (shape, r)
+
+
+def test_selection_probe_stays_inside_its_buffers(report):
+    # sum_smallest at d4c_kernel's five shapes, both assignments: ten selection rounds, and every refinement level with the
+    # whole row in the ranked list
+    assert len(report["select_probe"]) == 10
+    for shape, r in report["select_probe"].items():
+        assert r["rc"] == 0 and r["flag"] == 0 and r["record"] == [0, 0, 0, 0] and r["finite"], (shape, r)
+
+
+def test_spectral_probes_stay_inside_their_buffers(report):
+    # the replica with every bin a node (f0 around fs / 2: the mirror branch of the LDS form, several waves of the runs
+    # form) and the smoothing, both forms at every shape
+    assert len(report["spectral_probes"]) == 20
+    for shape, r in report["spectral_probes"].items():
         assert r["rc"] == 0 and r["flag"] == 0 and r["record"] == [0, 0, 0, 0] and r["finite"], (shape, r)
 
 

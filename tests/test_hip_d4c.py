@@ -37,7 +37,7 @@ def test_d4c_requiem(golden, tag):
 @pytest.mark.parametrize("fs", [16000, 48000])
 def test_d4c_rank_select_wide_dynamic_range(fs):
     """The band stage sums the smallest N/2 - boundary of the K power bins (world/d4c.py:206-208); the kernel selects
-    by IEEE exponent in rounds of 8 octaves.  Inputs whose band spectra spread over far more than 8 octaves — a clean
+    by IEEE exponent in rounds of 4 octaves (1 << WH_D4C_SEL_DB).  Inputs whose band spectra spread over far more — a clean
     click train, a smoothed one, and near-silence with one loud burst — must walk the further rounds and still agree with
     the oracle (which sorts).  These signals are also ill-conditioned for D4C as such (exact zeros between clicks: the
     centroid is divided by a smoothed power that is 1e-10 of its peak), so kernel and oracle agree to ~1e-5 ... 1e-4 dB
@@ -53,7 +53,7 @@ def test_d4c_rank_select_wide_dynamic_range(fs):
     t = np.arange(n) / fs
     rng = np.random.RandomState(5)
     # (checked on the oracle's spectra: on the frames that pass the love-train gate the 22 largest bins of these inputs
-    # span up to 12 / 14 / 20 octaves — two and three selection rounds)
+    # span up to 12 / 14 / 20 octaves — three, four and five selection rounds of 4 octaves)
     clicks = np.zeros(n)
     clicks[:: int(fs / 110)] = 0.8
     soft = np.convolve(clicks, np.hanning(9), mode="same") + 1e-6 * rng.randn(n)
