@@ -438,6 +438,34 @@ int wh_interp_contour(wh_ctx* ctx, void* stream, const wh_batch* b, const double
 int wh_regrid_rows(wh_ctx* ctx, void* stream, const wh_batch* src, const wh_batch* dst, const double* tp_src,
                    const double* tp_dst, const double* in, double* out, int k_bins, int positive_rule);
 
+/* ---- Frame alignment of parallel utterances: batched dynamic time warping (no counterpart in the reference) ------------ */
+/* Pair u aligns utterance u of `a` (N rows of xa) with utterance u of `b` (M rows of xb); rows are d doubles, row
+ * strides lda / ldb >= d, 1 <= d <= 64.  The arithmetic is fixed (tests/_dtw_reference.py is the same
+ * contract in NumPy, and the results agree bit for bit):
+ *   c(i,j) = sqrt(s), s summed from 0.0 over k = 0..d-1 of (a[i][k]-b[j][k])*(a[i][k]-b[j][k]), unfused, sqrt correctly
+ *     rounded;
+ *   D(0,0) = c(0,0), otherwise D(i,j) = c(i,j) + best, best among the predecessors that exist in the order D(i-1,j-1),
+ *     D(i-1,j), D(i,j-1), a later one replacing an earlier one only where it is strictly smaller; the one chosen is the
+ *     cell's back-pointer;
+ *   radius >= 1: cell (i,j) takes part iff |j*(N-1) - i*(M-1)| <= radius*max(N-1, M-1) (int64); the others hold +inf.
+ *     radius <= 0: the whole rectangle;
+ *   the path follows the back-pointers from (N-1,M-1) to (0,0) and is stored in forward order; on row 0 and on column
+ *     0 the only existing predecessor is taken whatever the values, so a path is well formed for non-finite input too;
+ *   map_b2a[j] = (i_lo + i_hi) / 2 over the path cells i_lo..i_hi that share j, map_a2b[i] likewise over those sharing i.
+ * Outputs (DEVICE): path_a / path_b hold batch-global frame indices (local index + the side's frame offset); the path
+ * of pair u occupies [h_path_off[u], h_path_off[u] + path_len[u]), and h_path_off (HOST) must leave each pair
+ * N_u + M_u - 1 entries; path_len / total_cost [n_utt] (total_cost = D(N-1,M-1)); map_a2b [frames of a] and map_b2a
+ * [frames of b] hold batch-global indices of the other side.  acc_out (may be NULL; a test hook for small shapes): D of
+ * every pair, row-major N x M at h_acc_off[u] (HOST).  The back-pointers (two bits per cell, rows padded to 16 cells) and
+ * the strip hand-off lines live in the context's scratch: the sum of 4 N_u ceil(M_u / 16) + 8 M_u bytes per call.  No atomics: a pair's result does not depend
+ * on the batch it is in.  One wave per pair: 1024 pairs of 2001 x 2001 frames, d = 39, take 45.7 ms on one MI355X (27.6 % of the
+ * FP64 vector issue rate), 23.7 ms inside radius 200; 64 pairs 40.8 ms.  Different utterance counts, an empty utterance on either side, d out of range or path offsets
+ * that leave too little room fail before anything is launched. */
+int wh_dtw(wh_ctx* ctx, void* stream, const wh_batch* a, const wh_batch* b, const double* xa, int64_t lda, const double* xb,
+           int64_t ldb, int d, int64_t radius, const int64_t* h_path_off, int64_t* path_a, int64_t* path_b,
+           int64_t* path_len, double* total_cost, int64_t* map_a2b, int64_t* map_b2a, double* acc_out,
+           const int64_t* h_acc_off);
+
 /* ---- 16-bit PCM at the batch boundary (the reference's WAV usage: example/prosody.py:12-13,57) ---------------------- */
 /* x[i] = pcm[i] / (2^15 - 1); pcm[i] = int16(trunc(y[i] * 2^15)) (low 16 bits, like NumPy's astype on the reference's
  * platform).  DEVICE pointers: the 2-byte samples cross PCIe instead of the 8-byte ones. */

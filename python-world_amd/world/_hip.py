@@ -92,6 +92,8 @@ SIGNATURES = {
     "wh_modify_duration": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
     "wh_interp_contour": (_int, [_vp, _vp, _vp, _vp, _c_i64p, _vp, _vp, _int, _vp, _vp]),
     "wh_regrid_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int]),
+    "wh_dtw": (_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _int, ctypes.c_int64, _c_i64p, _vp, _vp, _vp,
+                      _vp, _vp, _vp, _vp, _c_i64p]),
     "wh_pcm16_to_f64": (_int, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
     "wh_f64_to_pcm16": (_int, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
     "wh_swipe": (_int, [_vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp]),

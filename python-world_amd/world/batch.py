@@ -358,6 +358,18 @@ class BatchEncoding:
         from .compact import compact_encoding
         return compact_encoding(self, n0, lowhz, highhz, mcep_fs)
 
+    # ---- frame alignment with a parallel encoding (world/align.py) ------------------------------------------------
+    def align(self, other, n0=40, lowhz=0, highhz=8000, radius=None):
+        """Dynamic time warping of every utterance of this encoding against the same utterance of ``other`` (another
+        speaker's recording of the same sentences) over the mel-cepstra of the two spectrograms: encode_mcep with ``n0``
+        coefficients on both sides, coefficient 0 (the energy) dropped, Euclidean local cost, on the device
+        (world.align.align_device).  ``radius``: None, or the half-width of a band around the
+        diagonal.  Returns a world.align.Alignment: the paths, their costs, ``mcd_db()`` — the aligned mel-cepstral
+        distortion — the frame maps, and ``warp(self, other)``, this encoding on the other one's timing.  ValueError,
+        before the device is touched, for different sampling rates, utterance counts or runtimes and for n0 - 1 > 64."""
+        from .align import align_encodings
+        return align_encodings(self, other, n0, lowhz, highhz, radius)
+
     # ---- the manifold vocoder on the resident spectrogram (world/main.py:367-384; world/manifold.py) -------------
     def vae(self, encoder, decoder, mean, n0=40, window=0, lowhz=0, highhz=8000):
         """encode_mcep (n0 coefficients) of every frame, then the VAE's encoder and decoder in one launch on

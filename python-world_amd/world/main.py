@@ -473,6 +473,31 @@ class World(object):
         _hand_out(dats, y, y_off, True)
         return dats
 
+    # ---- frame alignment of parallel utterances (not in the reference's class; world/align.py) -------------------
+    @_hip.serialised
+    def align(self, dat_a, dat_b, n0=40, lowhz=0, highhz=8000, radius=None):
+        """Dynamic time warping of two encode() dicts of the same sentence over their mel-cepstra (encode_mcep with n0
+        coefficients, the energy dropped), on the device: {'path_a', 'path_b'} frame indices into each dict, 'cost' the
+        sum of the Euclidean local costs along the path and 'mcd' the aligned mel-cepstral distortion in dB.
+        ``radius``: None or the half-width of a band around the diagonal."""
+        from .align import align_dicts
+        return align_dicts([dat_a], [dat_b], n0, lowhz, highhz, radius)[0]
+
+    @_hip.serialised
+    def align_batch(self, dats_a, dats_b, n0=40, lowhz=0, highhz=8000, radius=None, devices=None):
+        """align() for lists of dicts, pair u aligning dats_a[u] with dats_b[u] in one batch: a list of result dicts."""
+        from .align import align_dicts
+        if devices is not None:
+            raise NotImplementedError("align_batch(devices=...): run one WorldBatch per device instead")
+        return align_dicts(dats_a, dats_b, n0, lowhz, highhz, radius)
+
+    def warp_to(self, dat_a, dat_b, alignment):
+        """dat_a on dat_b's timing: a new dict with dat_b's temporal_positions whose frame j holds dat_a's frame at the
+        middle of the stretch that ``alignment`` (align()'s result for the two) pairs with j — f0, vuv, spectrogram and
+        aperiodicity; decode() takes it."""
+        from .align import warp_dict
+        return warp_dict(dat_a, dat_b, alignment)
+
     # ---- modification (all in place on the dict, like the reference) ------------------------------------------
     def scale_pitch(self, dat, factor):
         """world/main.py:154-162."""
