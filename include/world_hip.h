@@ -67,6 +67,7 @@ int wh_copy_mapped(wh_ctx* ctx, void* stream, void* dst, const void* src, size_t
 #define WH_FLAG_NO_PULSE 3         /* an utterance produced no pulse (reference asserts, synthesis.py:131) */
 #define WH_FLAG_PULSE_OVERFLOW 4   /* more pulses than the pulse capacity, or more overlap-add rows than its row region holds */
 #define WH_FLAG_OOB 5              /* bounds build only (wh_bounds_build() == 1): a kernel indexed outside a named buffer */
+#define WH_FLAG_MLPG_PIVOT 6       /* wh_mlpg: a pivot of a system's LDL^T was not a positive finite number (non-finite or non-positive variances): that system's track is unspecified */
 int wh_take_flags(wh_ctx* ctx, void* stream, int32_t* h_flags16);
 /* The bounds build of the library (tools/build_variants.py ...:-DWH_BOUNDS=1; a test vehicle, never the shipped file):
  * the covered kernels index their buffers through checked pointers (csrc/wh_device.h, wh::ckp); an access outside a
@@ -465,6 +466,40 @@ int wh_dtw(wh_ctx* ctx, void* stream, const wh_batch* a, const wh_batch* b, cons
            int64_t ldb, int d, int64_t radius, const int64_t* h_path_off, int64_t* path_a, int64_t* path_b,
            int64_t* path_len, double* total_cost, int64_t* map_a2b, int64_t* map_b2a, double* acc_out,
            const int64_t* h_acc_off);
+
+/* ---- Dynamic features and maximum-likelihood parameter generation (no counterpart in the reference) ------------------- */
+/* What a statistical model of WORLD parameters is trained on and what turns its output back into a track.  Windows:
+ * h_win[n_win][2*half+1] (HOST), 1 <= n_win <= 4, half L in {0, 1, 2}; window 0 must be the static window (centre tap
+ * exactly 1.0, every other tap exactly 0.0: it gives W full column rank).  A tap that reaches outside its utterance is
+ * dropped (np.correlate(.., 'same')); no row of another utterance is ever read.  The arithmetic is fixed (DESIGN section
+ * 15; tests/_mlpg_reference.py is the same contract in NumPy, and the results agree bit for bit); every sum starts from
+ * 0.0 and is unfused, every product is rounded on its own and grouped as written:
+ *   features:  out[s][w*d + c] = sum over a = -L..L ascending with 0 <= s+a < T of win[w][a+L] * x[s+a][c];
+ *   generation, per system (utterance u of T frames, column c), band half-width B = 2L:
+ *     p_w[s] = 1.0 / var[s][w*d + c]  (one correctly rounded division);
+ *     R[t][t+k] = sum over w ascending, then s ascending in max(0, t+k-L) .. min(T-1, t+L), of
+ *                 (win[w][t-s+L] * p_w[s]) * win[w][t+k-s+L],   k = 0..B, t+k < T;
+ *     r[t]      = sum in the same order over s in max(0, t-L) .. min(T-1, t+L) of (win[w][t-s+L] * p_w[s]) * mean[s][w*d + c];
+ *     a sequential banded LDL^T without square roots, row t ascending with m = min(B, t); l[t][k] is the multiplier
+ *     L[t][t-k], q[t] = 1.0 / d[t] the pivot's only division, and every subtraction runs from the farthest predecessor
+ *     to the nearest:
+ *       for k = m .. 1:  v_k = R[t-k][t];  for n = m .. k+1: v_k -= v_n * l[t-k][n-k];  l[t][k] = v_k * q[t-k];
+ *       d[t] = R[t][t];  for k = m .. 1: d[t] -= v_k * l[t][k];      q[t] = 1.0 / d[t];
+ *       z[t] = r[t];     for k = m .. 1: z[t] -= l[t][k] * z[t-k];   y[t] = z[t] * q[t]   (the same sweep);
+ *     then from t = T-1 down:  c[t] = y[t];  for k = min(B, T-1-t) .. 1: c[t] -= l[t+k][k] * c[t+k].
+ * A pivot that is not a positive finite number raises WH_FLAG_MLPG_PIVOT; the call still returns, every access stays in
+ * range, and the other systems are untouched (a system's result never depends on the batch it is in).  An utterance
+ * without frames produces nothing.  x / mean / var / out: DEVICE, frame-major, row strides >= the row width (d for x and
+ * wh_mlpg's out, n_win*d for mean, var and wh_delta_features' out); ldv == 0: var is ONE row of n_win*d variances used for
+ * every frame.  d >= 1.  pivots_out (may be NULL; a test hook): d[t] of every system, [total_frames][d].  wh_mlpg keeps the
+ * multipliers in the context's scratch, 2L * 8 bytes per frame and column (y is kept in out), and out must not overlap
+ * mean or var.  One lane per system, 64 consecutive
+ * systems (u * d + c) per wave; the measured times are in DESIGN section 15.  Wrong arguments fail before anything is
+ * launched. */
+int wh_delta_features(wh_ctx* ctx, void* stream, const wh_batch* b, const double* x, int64_t ldx, int d, int n_win, int half,
+                      const double* h_win, double* out, int64_t ldo);
+int wh_mlpg(wh_ctx* ctx, void* stream, const wh_batch* b, const double* mean, int64_t ldm, const double* var, int64_t ldv,
+            int d, int n_win, int half, const double* h_win, double* out, int64_t ldo, double* pivots_out);
 
 /* ---- 16-bit PCM at the batch boundary (the reference's WAV usage: example/prosody.py:12-13,57) ---------------------- */
 /* x[i] = pcm[i] / (2^15 - 1); pcm[i] = int16(trunc(y[i] * 2^15)) (low 16 bits, like NumPy's astype on the reference's

@@ -94,6 +94,10 @@ SIGNATURES = {
     "wh_regrid_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int]),
     "wh_dtw": (_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _int, ctypes.c_int64, _c_i64p, _vp, _vp, _vp,
                       _vp, _vp, _vp, _vp, _c_i64p]),
+    "wh_delta_features": (_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, _int, _int, _int, ctypes.POINTER(_dbl), _vp,
+                                 ctypes.c_int64]),
+    "wh_mlpg": (_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _int, _int, _int, ctypes.POINTER(_dbl), _vp,
+                       ctypes.c_int64, _vp]),
     "wh_pcm16_to_f64": (_int, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
     "wh_f64_to_pcm16": (_int, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
     "wh_swipe": (_int, [_vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp]),
@@ -148,6 +152,7 @@ def same_frames(where, dense=(), **per_frame):
 
 # WH_FLAG_* of include/world_hip.h: sticky conditions raised by kernels instead of failing silently
 FLAG_STONEMASK_WINDOW, FLAG_EVENT_OVERFLOW, FLAG_NOISE_SHORT, FLAG_NO_PULSE, FLAG_PULSE_OVERFLOW, FLAG_OOB = range(6)
+FLAG_MLPG_PIVOT = 6
 FLAG_MESSAGES = {
     FLAG_STONEMASK_WINDOW: "StoneMask: a frame's f0 needs a longer analysis window than the one sized from min_f0 "
                            "(frame left unrefined)",
@@ -160,6 +165,8 @@ FLAG_MESSAGES = {
     FLAG_PULSE_OVERFLOW: "more pulses (or overlap-add rows) than pulse_cap provides for: trailing pulses / runs were dropped "
                          "(pass pulse_cap=world.synthesis.safe_pulse_cap(ny))",
     FLAG_OOB: "bounds build: a kernel indexed outside one of its buffers (world._hip.bounds_last() has the record)",
+    FLAG_MLPG_PIVOT: "MLPG: a pivot of a system's factorisation was not a positive finite number (variances must be "
+                     "positive and finite): that system's track is unspecified, every other system is unaffected",
 }
 
 

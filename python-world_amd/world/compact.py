@@ -162,6 +162,22 @@ class CompactEncoding:
         return BatchEncoding(rt, batch, ce.fs, ce.temporal_positions, ce.f0, ce.vuv, spec, ap, ce.fft_size, ce.is_requiem,
                              ce.frame_period, tp_host=None if ce.tp_host is None else np.array(ce.tp_host))
 
+    # ---- dynamic features and parameter generation (world/dynamics.py) ---------------------------------------------------
+    def dynamic_features(self, windows=None):
+        """What a statistical model of this encoding is trained on: {"mcep": [F][n_win n0], "band_ap": [F][n_win bands]},
+        column w * d + c being window w (static, delta, delta-delta for the default HTS_WINDOWS) over column c; no window
+        reaches across an utterance.  Device tensors; the encoding must be resident."""
+        from .dynamics import HTS_WINDOWS, compact_dynamic_features
+        return compact_dynamic_features(self, HTS_WINDOWS if windows is None else windows)
+
+    def with_trajectories(self, mcep=None, band_ap=None, windows=None):
+        """A new CompactEncoding whose 'mcep' / 'band_ap' are the maximum-likelihood tracks (world.dynamics.mlpg_device) of
+        the given (mean, var) pairs — mean [F][n_win d] laid out like dynamic_features(), var the same shape or one row
+        [n_win d]; None keeps this encoding's tensor.  f0, vuv, the voicing gate and the frame times are carried over:
+        the result is ready for expand(wb) -> decode_device."""
+        from .dynamics import HTS_WINDOWS, compact_with_trajectories
+        return compact_with_trajectories(self, mcep, band_ap, HTS_WINDOWS if windows is None else windows)
+
     # ---- files (host only) -------------------------------------------------------------------------------------------
     def save_npz(self, path):
         """One .npz for the batch: the tensors, the per-utterance frame offsets and the parameters."""

@@ -498,6 +498,27 @@ class World(object):
         from .align import warp_dict
         return warp_dict(dat_a, dat_b, alignment)
 
+    # ---- dynamic features and parameter generation (not in the reference's class; world/dynamics.py) ---------------
+    @_hip.serialised
+    def delta_features(self, x, windows=None, devices=None):
+        """Static + delta + delta-delta rows (any 1 .. 4 windows of half-width <= 2, the first the static one; default
+        world.dynamics.HTS_WINDOWS) of one utterance x [T][d] or of a list of them, on the device: [T][n_win d], column
+        w * d + c being window w over column c; a tap that reaches outside the utterance is dropped."""
+        from .dynamics import HTS_WINDOWS, delta_features_numpy
+        if devices is not None:
+            raise NotImplementedError("delta_features(devices=...): run one WorldBatch per device instead")
+        return delta_features_numpy(x, HTS_WINDOWS if windows is None else windows)
+
+    @_hip.serialised
+    def mlpg(self, mean, var, windows=None, devices=None):
+        """Maximum-likelihood parameter generation: the track [T][d] that is most likely under the means [T][n_win d] and
+        variances (the same shape, or one row [n_win d] for every frame) of its static and dynamic features — one
+        utterance or a list of them, solved on the device (one banded LDL' per utterance and column)."""
+        from .dynamics import HTS_WINDOWS, mlpg_numpy
+        if devices is not None:
+            raise NotImplementedError("mlpg(devices=...): run one WorldBatch per device instead")
+        return mlpg_numpy(mean, var, HTS_WINDOWS if windows is None else windows)
+
     # ---- modification (all in place on the dict, like the reference) ------------------------------------------
     def scale_pitch(self, dat, factor):
         """world/main.py:154-162."""
