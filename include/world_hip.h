@@ -102,13 +102,13 @@ int wh_fft_engine_probe(wh_ctx* ctx, void* stream, int kind, int n, int nt, int 
  * FFT passes' [k][r] tables behind them) copied to HOST memory as (re, im) doubles.  h_out == NULL: returns the number of
  * entries; otherwise n_entries must be that number, and 0 is returned on success. */
 int wh_twiddle_read(wh_ctx* ctx, double* h_out, int64_t n_entries);
-/* Test hook: D4C's rank selection (sum_smallest, csrc/wh_d4c.hip) on DEVICE data, with the template arguments d4c_kernel of
+/* Test hook: D4C's rank selection (sum_smallest, csrc/wh_d4c_select.h; the hook: csrc/wh_d4c_probe.hip) on DEVICE data, with the template arguments d4c_kernel of
  * transform length n (512 ... 8192) gives it.  `count` rows of K = n / 2 + 1 non-negative values, one workgroup each;
  * out[c] = (sum of the m smallest values of row c, sum of all K), 1 <= m <= K - 1.  layout 0 hands the values to the threads
  * as the band stage does (job i of thread t: bins t + i FT and n / 2 - (t + i FT)); layout 1 puts bin k on thread
  * (K - 1 - k) % FT, slots filled in the order of k. */
 int wh_d4c_select_probe(wh_ctx* ctx, void* stream, int n, int layout, int m, const double* vals, double* out, int64_t count);
-/* Test hook: the run-resident spectral helpers of csrc/wh_d4c.hip on DEVICE data.  `count` half spectra of K = n / 2 + 1
+/* Test hook: the run-resident spectral helpers of csrc/wh_d4c_runs.h on DEVICE data (csrc/wh_d4c_probe.hip).  `count` half spectra of K = n / 2 + 1
  * bins in `in`, one workgroup each, K results each in `out`.  which 0: low_band_replica_runs<n> with f0[c] and reach =
  * reach_or_half[c]; which 1: fill_mirrored_runs<n> and the sliding band sum BandWindow::run of half-width reach_or_half[c]
  * Hz (not divided by the width; half-widths outside [0, fs] give zeros), f0 unused.  f0, reach_or_half: DEVICE arrays of

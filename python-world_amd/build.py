@@ -28,6 +28,9 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 #     differs from NumPy's pocketfft at the 1e-16 level with or without contraction, so a frame whose ratio lies within
 #     ~1e-15 of the threshold can fall on either side either way).  Worth 1.1 % of the config-2 step (round 5: d4c
 #     4.64 -> 4.56 ms, cheaptrick 1.14 -> 1.11, responses 3.45 -> 3.43).
+#   * wh_apbands.hip (the expansion of stored band aperiodicity: wh_apbands.h, the interpolation it shares with d4c_kernel,
+#     pins its own contraction) and wh_d4c_probe.hip (the test hooks of wh_d4c_select.h / wh_d4c_runs.h) were parts of
+#     wh_d4c.hip and keep its flags: the code they hold is compiled as it was there.
 #   * wh_synthesis.hip and wh_requiem.hip are built unfused (Philox, the Requiem excitation and the gathers round like the
 #     reference) and fuse by `#pragma clang fp contract(fast)` inside min_phase_response (wh_minphase.h), response_pulse,
 #     response_pair and noise_conv_groups only.
@@ -35,6 +38,8 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 # stay unfused: voicing decisions and pulse positions are bit-exact against the reference.
 TU_FLAGS = {
     "wh_d4c.hip": ["-ffp-contract=fast-honor-pragmas"],
+    "wh_apbands.hip": ["-ffp-contract=fast-honor-pragmas"],
+    "wh_d4c_probe.hip": ["-ffp-contract=fast-honor-pragmas"],  # (a test hook: the D4C headers as wh_d4c.hip compiles them)
     "wh_cheaptrick.hip": ["-ffp-contract=fast-honor-pragmas"],
     "wh_fft_probe.hip": ["-ffp-contract=fast-honor-pragmas"],  # (a test hook: the transforms as most of their callers compile them)
     "wh_spectral_probe.hip": ["-ffp-contract=fast-honor-pragmas"],  # (a test hook: wh_spectral.h as wh_cheaptrick.hip compiles it)

@@ -2,9 +2,9 @@
 //
 //     10 ** (interp1d(coarse_axis, [-60, coarse..., -1e-12])(k * fs / fft_size) / 20),   coarse_axis = [0, fi, ..., nap fi, fs / 2]
 //
-// is written.  d4c_kernel (the tail of a frame) and ap_from_bands_kernel (wh_aperiodicity_from_bands: the expansion of a
-// stored band aperiodicity) both evaluate it through these functions, in one translation unit and under one set of flags,
-// so the expansion reproduces D4C's dense rows bit for bit.  Every function keeps `#pragma clang fp contract(off)`
+// is written.  d4c_kernel (wh_d4c.hip: the tail of a frame) and ap_from_bands_kernel (wh_apbands.hip,
+// wh_aperiodicity_from_bands: the expansion of a stored band aperiodicity) both evaluate it through these functions, in two
+// translation units under one set of flags (build.py), so the expansion reproduces D4C's dense rows bit for bit.  Every function keeps `#pragma clang fp contract(off)`
 // whatever the unit's setting: with a 0 dB band a fused slope * dx + y_lo can land an ulp ABOVE 0 dB, i.e. an
 // aperiodicity above 1 (the reference's interpolation, d4c.py:58-59, is unfused NumPy).
 #pragma once

@@ -488,7 +488,8 @@ __device__ __forceinline__ void dft_small(double2 (&v)[R]) {
 // transform on 256 threads is faster as 4-4-4-4-2 on 128 lanes than as 8-8-8 on 64: its passes are latency-,
 // not throughput-bound), else 4, else 2.
 // MAXR caps the radix for a kernel whose register budget is set elsewhere (radix-4 butterflies hold half as many
-// operands): d4c_kernel at 128 VGPRs takes the radix-8 plan up to N = 1024 and radix 4 beyond (wh_d4c.hip).
+// operands).  No kernel caps it today — d4c_kernel, the last to, settled on radix 8 at every length —; the radix-4 plans
+// stay built and tested as engine functions (wh_fft_probe.hip).
 template <int N, int NT, int NS, int MAXR = 8>
 struct FftRadix {
   static constexpr int value = (MAXR >= 8 && NS * 8 <= N && N / 8 >= NT / 2) ? 8 : (NS * 4 <= N ? 4 : 2);

@@ -86,7 +86,7 @@ int launch_probe(wh_ctx* ctx, hipStream_t st, const double* in, double* out, lon
   X(0, 4096, 512, 512, 8, 0) X(0, 8192, 512, 512, 8, 0) X(0, 4096, 256, 256, 8, 1)                                      \
   /* what fft_lds_wave runs on its one wave; the workgroup-wide twin of the register-fed (1024, 128) */                 \
   WH_PROBE_FWD_INV(X, 512, 64, 64, 8) X(0, 1024, 128, 128, 8, 0)                                                        \
-  /* tools/build_variants.py: d4c_kernel's radix-4 plans (-DWH_D4C_MAXR=4 / -DWH_D4C_RMAXR=4), natural layout */        \
+  /* the radix-4 plans (MAXR = 4, natural layout; no caller today): D4C's fft_lds and rfft_lds shapes */                \
   X(0, 2048, 256, 256, 4, 0) X(0, 4096, 512, 512, 4, 0) X(0, 8192, 512, 512, 4, 0)                                      \
   X(2, 4096, 256, 256, 4, 0) X(2, 8192, 512, 512, 4, 0) X(2, 16384, 512, 512, 4, 0)                                     \
   /* fft_lds_wave: response_kernel<1024>'s chains (GT 128 and 256 in a 256-thread workgroup), and a one-wave workgroup */ \

@@ -8,6 +8,7 @@
 
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/world_hip.h"
@@ -112,6 +113,25 @@ inline int allow_lds(K kernel, size_t bytes) {
   if (bytes <= 65536) return 0;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   return e == hipSuccess ? 0 : fail("hipFuncSetAttribute", e);
+}
+// f(std::integral_constant<int, N>()) for the transform length fft_size = N of a kernel family that is instantiated at the
+// powers of two from 512 to MAXN (4096: the synthesis kernels; 8192: D4C and its gate); false: not one of them.
+template <int MAXN = 4096, class F>
+inline bool dispatch_fft_size(int fft_size, F&& f) {
+  static_assert(MAXN == 4096 || MAXN == 8192, "the lengths the kernels are built at");
+  switch (fft_size) {
+    case 512: f(std::integral_constant<int, 512>()); return true;
+    case 1024: f(std::integral_constant<int, 1024>()); return true;
+    case 2048: f(std::integral_constant<int, 2048>()); return true;
+    case 4096: f(std::integral_constant<int, 4096>()); return true;
+    case 8192:
+      if constexpr (MAXN >= 8192) {
+        f(std::integral_constant<int, 8192>());
+        return true;
+      }
+      return false;
+    default: return false;
+  }
 }
 // RAII bracket around one kernel launch: records a start/stop event pair on the launch stream when
 // profiling is enabled (zero cost otherwise).

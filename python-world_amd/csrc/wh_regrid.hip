@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void regrid_plan_kernel(const double* __restri
 
 // The row kernel is memory-bound: per output row one or two source rows in, one row out.  A workgroup owns `rows`
 // consecutive destination frames (an even number), takes their plan entries to LDS and walks the group's bins as PAIRS
-// of the flat output, as ap_from_bands_kernel does (wh_d4c.hip): K is odd for the dense tensors, so a single row is
+// of the flat output, as ap_from_bands_kernel does (wh_apbands.hip): K is odd for the dense tensors, so a single row is
 // not 16-byte aligned, but an even number of rows is — every pair is one 16-byte store whichever rows its two bins
 // belong to.  The source side of a pair that lies inside one row is one 16-byte load where its address allows
 // (rows of odd K alternate) and two 8-byte loads of the same 16 bytes where it does not.  The scalar instantiation

@@ -1,7 +1,7 @@
 // Test hook for the LDS forms of wh_spectral.h: wh_spectral_probe runs low_band_replica<FT>, or fill_mirrored<FT, N> followed
 // by BandWindow::init / run<KR>, on caller data at CheapTrick's (N, FT) pairs, one frame per workgroup, with the LDS block
 // laid out as cheaptrick_kernel lays it out.  Nothing in the library calls it (tests/test_hip_spectral_helpers.py does; the
-// run-resident forms of wh_d4c.hip have wh_d4c_runs_probe).  Compiled with wh_cheaptrick.hip's flags (build.py), so the
+// run-resident forms of wh_d4c_runs.h have wh_d4c_runs_probe).  Compiled with wh_cheaptrick.hip's flags (build.py), so the
 // a * b + c of the interpolation and of the window's two fractional terms fuse here as they do there.
 #include "wh_host.h"
 #include "wh_spectral.h"

@@ -2,7 +2,6 @@
 // records, the frame-time interpolation, the workspace layout of the time base and the host helpers that cross units.
 // Include after wh_host.h and wh_device.h.
 #pragma once
-#include <type_traits>
 
 namespace wh {
 
@@ -107,18 +106,7 @@ __device__ __forceinline__ int first_pulse_at(const int64_t* __restrict__ pi, in
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// f(std::integral_constant<int, N>()) for the transform length fft_size = N of the synthesis kernels; false: not one of them.
-template <class F>
-inline bool dispatch_fft_size(int fft_size, F&& f) {
-  switch (fft_size) {
-    case 512: f(std::integral_constant<int, 512>()); return true;
-    case 1024: f(std::integral_constant<int, 1024>()); return true;
-    case 2048: f(std::integral_constant<int, 2048>()); return true;
-    case 4096: f(std::integral_constant<int, 4096>()); return true;
-    default: return false;
-  }
-}
-
+// (wh::dispatch_fft_size, the switch over the kernels' transform lengths: wh_host.h)
 // scratch of the pulse stage: crossing masks (one byte per 4 samples) and per-tile counts (wh_timebase.hip: launch_pulses)
 size_t pulse_scratch_bytes(int B, int64_t max_ny);
 

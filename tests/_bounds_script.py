@@ -139,7 +139,7 @@ def main():
         probe["-".join(str(v) for v in shape)] = {"rc": rc, "flag": fl[_hip.FLAG_OOB], "record": list(_hip.bounds_last()),
                                                   "finite": bool(np.all(np.isfinite(y_d.cpu().numpy())))}
     out["fft_probe"] = probe
-    # ---- the selection probe and the two spectral probes (csrc/wh_d4c.hip, csrc/wh_spectral_probe.hip): one call per shape —
+    # ---- the selection probe and the two spectral probes (csrc/wh_d4c_probe.hip, csrc/wh_spectral_probe.hip): one call per shape —
     # exponents over 39 octaves (every selection round) and all values equal (every refinement level, the whole row in the
     # ranked list); the replica with f0 around fs / 2 (every bin a node, the mirror branch of the LDS form) -----------------
     def taken(rc, y_d):

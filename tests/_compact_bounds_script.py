@@ -1,5 +1,5 @@
 """Helper of tests/test_hip_compact_bounds.py: runs in a process whose WH_LIB is the bounds build
-(tools/build_variants.py bounds=...;wh_d4c:-DWH_BOUNDS=1: ap_from_bands_kernel and ap_gate_kernel index their global and
+(tools/build_variants.py bounds=...;wh_apbands:-DWH_BOUNDS=1: ap_from_bands_kernel and ap_gate_kernel index their global and
 LDS buffers through wh::ckp there).  Prints one JSON line."""
 import json
 import os

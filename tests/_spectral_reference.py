@@ -2,7 +2,7 @@
 comparators the GPU tests judge the kernels with (tests/test_hip_d4c_select.py, tests/test_hip_spectral_helpers.py;
 tests/test_spectral_reference_host.py checks this file against the oracle and against deliberate mistakes, on the CPU).
 
-Selection (sum_smallest, csrc/wh_d4c.hip; world/d4c.py:206-208): sort, then the exactly rounded sum of the first m values
+Selection (sum_smallest, csrc/wh_d4c_select.h; world/d4c.py:206-208): sort, then the exactly rounded sum of the first m values
 (math.fsum), or Python integers where the data are integers.  The bound for data that are not: summing K non-negative
 terms in ANY order is off by at most (K - 1) u times the sum, u = 2^-53 (each of the K - 1 additions rounds a partial sum
 that is at most the total; first order in u) — so a selection that is right differs from the reference by no more than
@@ -32,6 +32,7 @@ import numpy as np
 
 LD = np.longdouble
 U = 2.0 ** -53
+D4C_FT = {512: 256, 1024: 128, 2048: 256, 4096: 512, 8192: 512}  # threads per frame at N: ft_of(n), csrc/wh_d4c_types.h
 
 
 # ---- selection ----------------------------------------------------------------------------------------------------------
@@ -74,7 +75,7 @@ def d4c_fft_size(fs):
 
 
 def d4c_boundary(fs, n=None):
-    """`boundary` of d4c_launch_const (csrc/wh_d4c.hip; world/d4c.py:197-199) at d4c()'s own transform length and band
+    """`boundary` of d4c_launch_const (csrc/wh_d4c_types.h; world/d4c.py:197-199) at d4c()'s own transform length and band
     interval for the rate: the band stage leaves boundary + 1 values out."""
     n = n or d4c_fft_size(fs)
     interval = 2000 if fs < 16000 else 3000

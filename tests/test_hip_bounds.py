@@ -12,7 +12,7 @@ records; an f0 sweep from 1 Hz to 1.5 fs at five (rate, transform) pairs — cal
 estimators never return (world/cheaptrick.py:64-131 takes any f0) — stays inside every buffer; config 2 at its full
 size, a Harvest + Requiem batch and a 48 kHz utterance run clean; the transform probe (csrc/wh_fft_probe.hip), one launch
 each of a handful of shapes, stays inside its LDS buffers and the twiddle block; the selection probe and the two spectral
-probes (csrc/wh_d4c.hip, csrc/wh_spectral_probe.hip), one call per shape on the inputs that reach furthest — every selection
+probes (csrc/wh_d4c_probe.hip, csrc/wh_spectral_probe.hip), one call per shape on the inputs that reach furthest — every selection
 round and refinement level, the replica with every bin a node — stay inside theirs."""
 import json
 import os
@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 BOUNDS_TUS = ("wh_api", "wh_cheaptrick", "wh_stonemask", "wh_harvest", "wh_hv_front", "wh_hv_refine", "wh_hv_contour", "wh_timebase", "wh_synthesis", "wh_requiem", "wh_d4c",
-              "wh_fft_probe", "wh_spectral_probe")
+              "wh_apbands", "wh_d4c_probe", "wh_fft_probe", "wh_spectral_probe")
 VARIANT = os.path.join(ROOT, "python-world_amd", "lib", "variants", "libworld_hip_bounds.so")
 
 

@@ -1,6 +1,6 @@
 """GPU: ap_from_bands_kernel and ap_gate_kernel in the bounds build (csrc/wh_device.h, wh::ckp: every global and LDS
-buffer of the two kernels is a checked pointer under -DWH_BOUNDS=1).  They live in wh_d4c.hip, so the variant is the one
-tests/test_hip_bounds.py builds (wh_api and wh_d4c instrumented, among others).  The inputs of
+buffer of the two kernels is a checked pointer under -DWH_BOUNDS=1).  They live in wh_apbands.hip, so the variant is the one
+tests/test_hip_bounds.py builds (wh_api, wh_d4c and wh_apbands instrumented, among others).  The inputs of
 tests/test_hip_compact.py's bitwise and end-to-end tests: zero out-of-range records, and D4C's bits still."""
 import json
 import os

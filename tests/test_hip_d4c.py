@@ -37,7 +37,7 @@ def test_d4c_requiem(golden, tag):
 @pytest.mark.parametrize("fs", [16000, 48000])
 def test_d4c_rank_select_wide_dynamic_range(fs):
     """The band stage sums the smallest N/2 - boundary of the K power bins (world/d4c.py:206-208); the kernel selects
-    by IEEE exponent in rounds of 4 octaves (1 << WH_D4C_SEL_DB).  Inputs whose band spectra spread over far more — a clean
+    by IEEE exponent in rounds of 4 octaves (1 << kSelDb, csrc/wh_d4c_select.h).  Inputs whose band spectra spread over far more — a clean
     click train, a smoothed one, and near-silence with one loud burst — must walk the further rounds and still agree with
     the oracle (which sorts).  These signals are also ill-conditioned for D4C as such (exact zeros between clicks: the
     centroid is divided by a smoothed power that is 1e-10 of its peak), so kernel and oracle agree to ~1e-5 ... 1e-4 dB

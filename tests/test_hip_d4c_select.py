@@ -1,4 +1,4 @@
-"""GPU: D4C's rank selection (sum_smallest, csrc/wh_d4c.hip) on its own, through wh_d4c_select_probe, with the template
+"""GPU: D4C's rank selection (sum_smallest, csrc/wh_d4c_select.h) on its own, through wh_d4c_select_probe, with the template
 arguments of every d4c_kernel instance (n = 512 ... 8192: K = 257 ... 4097 values on 256 / 128 / 256 / 512 / 512 threads in
 2 / 6 / 6 / 6 / 10 slots) and two assignments of the values to threads, against sort-and-sum (tests/_spectral_reference.py).
 
@@ -31,7 +31,7 @@ import _spectral_reference as S
 
 pytestmark = pytest.mark.gpu
 
-FT = {512: 256, 1024: 128, 2048: 256, 4096: 512, 8192: 512}  # ft_of(n), csrc/wh_d4c.hip
+FT = S.D4C_FT  # ft_of(n), csrc/wh_d4c_types.h
 SLOTS = {512: 2, 1024: 6, 2048: 6, 4096: 6, 8192: 10}
 RATES = (8000, 16000, 22050, 32000, 48000, 96000)
 EXACT = ("octaves", "all_equal", "permutation", "two_valued", "five_positive", "zeros", "first_wave_30", "last_wave_30",

@@ -1,6 +1,6 @@
 """GPU: the rectangular smoothing (BandWindow) and the low-band replica of CheapTrick and D4C on their own, in both forms —
 the LDS form of csrc/wh_spectral.h through wh_spectral_probe at cheaptrick_kernel's (N, FT) pairs, the run-resident form of
-csrc/wh_d4c.hip through wh_d4c_runs_probe at d4c_kernel's N — against tests/_spectral_reference.py (where the bounds used
+csrc/wh_d4c_runs.h through wh_d4c_runs_probe at d4c_kernel's N — against tests/_spectral_reference.py (where the bounds used
 here are derived).
 
   smoothing, bit for bit   integer spectra at dyadic fs / N, half-widths that are odd multiples of fs / N / 2 (f_lo = f_hi = 0)
@@ -28,7 +28,7 @@ import _spectral_reference as S
 pytestmark = pytest.mark.gpu
 
 LD = S.LD
-D4C_FT = {512: 256, 1024: 128, 2048: 256, 4096: 512, 8192: 512}  # ft_of(n), csrc/wh_d4c.hip
+D4C_FT = S.D4C_FT  # ft_of(n), csrc/wh_d4c_types.h
 # (form, n, ft): CheapTrick's pairs in the LDS form, D4C's in the run-resident one
 SHAPES = [("lds", 256, 128), ("lds", 512, 128), ("lds", 1024, 128), ("lds", 2048, 256), ("lds", 4096, 256)] + [
     ("runs", n, D4C_FT[n]) for n in sorted(D4C_FT)]

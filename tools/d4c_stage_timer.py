@@ -24,6 +24,9 @@ for it in range(3):
     torch.cuda.synchronize()
     lib.wh_debug_d4c_stages(buf, 1)
 v = np.array(list(buf), dtype=np.float64)
+# (stage index, label) in kernel order; the indices are enum D4cStage of csrc/wh_d4c_types.h: kStWindows = 7, kStGateFft = 8,
+# kStGateFold = 0, kStCentroidA / B = 1 / 2, kStReplica = 3, kStSmooth = 4, kStBandFill = 12, kStBandFft = 13,
+# kStBandPower = 9, kStSelect = 5, kStOutput = 6, kStWinWalk = 10, kStWinReduce = 11
 order = [(7, "start-up + the two stage-1 windows"), (8, "fused gate/power FFT"), (0, "gate reduction + power fold"),
          (1, "centroid A (window + FFT + fold)"), (2, "centroid B"), (3, "low-band replica (cent)"),
          (4, "smoothing: power replica + 3 sliding windows"), (12, "band: shaped group delay x Nuttall window -> buffer"), (13, "band: real FFT"), (9, "band: power"), (5, "rank select"),
