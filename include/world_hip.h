@@ -83,11 +83,11 @@ int wh_bounds_selftest(wh_ctx* ctx, void* stream);
 /* Test hook: the spectral kernels' own log / exp / sincospi (csrc/wh_math.h: a few ulp, a third of the device library's
  * instructions) applied to a DEVICE array: which = 0 log -> out[n], 1 exp -> out[n], 2 (sin, cos)(pi x) -> out[2n]. */
 int wh_math_probe(wh_ctx* ctx, void* stream, int which, const double* in, double* out, int64_t n);
-/* Test hook: the wave-local FFT engine (wh::fft_lds_wave, csrc/wh_device.h) on DEVICE data: `count` unnormalised complex
+/* Test hook: the wave-local FFT engine (wh::fft_lds_wave, csrc/wh_fft.h) on DEVICE data: `count` unnormalised complex
  * transforms of n = 512 points, interleaved (re, im) doubles, in -> out; inverse = 1: exp(+2 pi i k j / n), not divided by
  * n.  (gt, snt): threads per transform group and per workgroup, one of (64, 64), (128, 256), (256, 256). */
 int wh_fft_probe(wh_ctx* ctx, void* stream, int n, int gt, int snt, int inverse, const double* in, double* out, int64_t count);
-/* Test hook: the workgroup-wide transforms of csrc/wh_device.h on DEVICE data, at the shapes the kernels instantiate them
+/* Test hook: the workgroup-wide transforms of csrc/wh_fft.h on DEVICE data, at the shapes the kernels instantiate them
  * with (csrc/wh_fft_probe.hip lists them; any other shape fails with a message).  kind 0: fft_lds<n, inverse, nt, snt, maxr>,
  * n complex -> n complex; 1: fft_lds_from_regs<n, false, nt, maxr>, the same, the input read straight into the registers of
  * the first pass (x[q] = element tid + q nt); 2: rfft_lds<n, nt, snt, maxr>, n reals -> n / 2 + 1 complex; 3:

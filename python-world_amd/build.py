@@ -33,7 +33,9 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 #     wh_d4c.hip and keep its flags: the code they hold is compiled as it was there.
 #   * wh_synthesis.hip and wh_requiem.hip are built unfused (Philox, the Requiem excitation and the gathers round like the
 #     reference) and fuse by `#pragma clang fp contract(fast)` inside min_phase_response (wh_minphase.h), response_pulse,
-#     response_pair and noise_conv_groups only.
+#     response_pair and noise_conv_groups only (wh_resp_pulse.h, wh_resp_pair.h).
+#   * wh_peak.hip and wh_philox_probe.hip were parts of wh_synthesis.hip, which has no entry below (it contracts by
+#     pragma): they need none either.
 # The F0 stages (DIO, StoneMask, Harvest — wh_harvest.hip, wh_hv_front.hip, wh_hv_refine.hip, wh_hv_contour.hip —, SWIPE') and the synthesis TIME BASE (wh_timebase.hip: no pragma anywhere in it)
 # stay unfused: voicing decisions and pulse positions are bit-exact against the reference.
 TU_FLAGS = {

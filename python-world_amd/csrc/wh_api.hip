@@ -3,6 +3,7 @@
 #include <string.h>
 
 #include "wh_device.h"
+#include "wh_fft.h"
 #include "wh_host.h"
 #include "wh_math.h"
 
@@ -186,7 +187,7 @@ int wh_ctx_create(int device, wh_ctx** out) {
     // n = 1024 on: tests/test_hip_fft_engine.py)
     for (int k = n / 2 + 1; k < n; ++k) tw[n + k] = make_double2(tw[n + n - k].x, -tw[n + n - k].y);
   }
-  // behind them the FFT passes' [k][r] tables (wh_device.h, fft_ptw_offset): copies of the size-M tables' entries k r
+  // behind them the FFT passes' [k][r] tables (wh_device.h: fft_ptw_offset; wh_fft.h reads them): copies of the size-M tables' entries k r
   for (int R = 2; R <= 8; R <<= 1)
     for (int m = R; m <= WH_MAX_FFT; m <<= 1)
       for (int k = 0; k < m / R; ++k)

@@ -6,6 +6,8 @@
 // Reference: get_raw_event (world/dio.py:128-140) / CalculateRawEvent (world/harvest.py:252-269).
 #pragma once
 #include "wh_events.h"
+#include "wh_fft.h"
+#include "wh_reduce.h"
 #include "wh_host.h"
 #include "wh_hv_types.h"  // kOlsN, kOlsValid: the overlap-save geometry, which also sizes Harvest's workspace
 

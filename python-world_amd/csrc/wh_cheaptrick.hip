@@ -1,31 +1,24 @@
 // CheapTrick spectral envelope — one 128-thread workgroup per frame (256 from N = 2048), everything between the
 // waveform gather and the final envelope stays in LDS (12*N bytes): window → real FFT → power →
 // low-band replica → sliding-window smoothing → log → real FFT → lifter → inverse real FFT → exp.
-// All three transforms run as N/2-point complex FFTs on sample pairs (wh_device.h: rfft_lds / irfft_lds).
+// All three transforms run as N/2-point complex FFTs on sample pairs (wh_fft.h: rfft_lds / irfft_lds).
 // Replaces cheaptrick()/estimate_one_slice() of the reference (world/cheaptrick.py:9-157).
 #include "wh_host.h"
 #include "wh_math.h"
 // (the 2 x 513 transcendentals of a frame: wh_math.h's flog, the device library's exp)
 #include "wh_spectral.h"
+#include "wh_fft.h"
+#include "wh_reduce.h"
 
 namespace {
 
-#ifndef WH_FT_CHEAPTRICK
-#define WH_FT_CHEAPTRICK 128
-#endif
 // Threads cooperating on one frame: 128 up to N = 1024, 256 from N = 2048 (measured on configs 2 and 5).
-constexpr int ft_ct(int n) { return n >= 2048 ? 2 * WH_FT_CHEAPTRICK : WH_FT_CHEAPTRICK; }
+constexpr int ft_ct(int n) { return n >= 2048 ? 256 : 128; }
 
 // waves per SIMD the register allocation leaves room for: at N <= 1024 the kernel wants 84 VGPRs (5 waves); capped at
 // 80 it runs 6 (1.31 -> 1.25 ms at config 2; 7 -> 72 VGPRs, 2 spilled: 1.28; 8: 1.46).  Longer transforms keep what
 // they ask for.
-#ifndef WH_CT_MINW
-#define WH_CT_MINW 6
-#endif
-#ifndef WH_CT_MINW_MAXN
-#define WH_CT_MINW_MAXN 1024
-#endif
-constexpr int ct_minw(int n) { return n <= WH_CT_MINW_MAXN ? WH_CT_MINW : 1; }
+constexpr int ct_minw(int n) { return n <= 1024 ? 6 : 1; }
 template <int N>
 __global__ __launch_bounds__(ft_ct(N), ct_minw(N)) void cheaptrick_kernel(
     const double* __restrict__ x, const int64_t* __restrict__ x_off, const int32_t* __restrict__ frame_utt,

@@ -10,6 +10,8 @@
 // timer), wh_d4c_window.h (the analysis windows), wh_d4c_select.h (the rank selection), wh_d4c_runs.h (the run-resident
 // spectral helpers).  Every transform call of D4C is in this file.
 #include "wh_d4c_types.h"
+#include "wh_fft.h"
+#include "wh_reduce.h"
 #include "wh_d4c_window.h"
 #include "wh_d4c_select.h"
 #include "wh_d4c_runs.h"

@@ -2,6 +2,7 @@
 // counting helpers.  d4c_frame's band stage calls it; wh_d4c_select_probe (wh_d4c_probe.hip) runs it on caller data.
 // Include after wh_d4c_types.h.
 #pragma once
+#include "wh_reduce.h"
 
 namespace wh {
 

@@ -5,7 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-// The thread index as the FFT / reduction helpers of wh_device.h see it: an opaque read.  d4c_kernel runs four
+// The thread index as the FFT / reduction helpers of wh_fft.h / wh_reduce.h see it: an opaque read.  d4c_kernel runs four
 // transforms and four windows per frame through the same helpers; with the plain threadIdx.x the compiler recognises
 // the per-thread LDS addresses (eight swizzled store addresses and eight load addresses per radix-8 pass), twiddle
 // offsets and index-to-double conversions as common subexpressions of all of them, computes them once and parks them

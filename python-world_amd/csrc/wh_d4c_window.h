@@ -3,6 +3,7 @@
 // The two are kept as two routines on purpose: one shared helper moved 15 of the unit's 28 functions.
 // Include after wh_d4c_types.h.
 #pragma once
+#include "wh_reduce.h"
 
 namespace wh {
 

@@ -1,9 +1,9 @@
-// Test hooks for the shared transform engine of wh_device.h: wh_fft_engine_probe runs fft_lds / fft_lds_from_regs / rfft_lds /
+// Test hooks for the shared transform engine of wh_fft.h: wh_fft_engine_probe runs fft_lds / fft_lds_from_regs / rfft_lds /
 // irfft_lds / fft_lds_wave on caller data at the (N, NT, SNT, MAXR, direction) shapes the kernels instantiate them with, one transform per
 // NT-thread group of an SNT-thread workgroup; wh_twiddle_read copies the context's twiddle block to the host.  Nothing in
 // the library calls either (tests/test_hip_fft_engine.py does).  Compiled with the spectral units' flags (build.py): the
 // complex products of the passes fuse here as they do in CheapTrick, D4C and the response chains.
-#include "wh_device.h"
+#include "wh_fft.h"
 #include "wh_host.h"
 
 namespace {

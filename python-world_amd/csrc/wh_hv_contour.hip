@@ -8,6 +8,7 @@
 
 #include "wh_tid.h"  // (the opaque thread index the old single Harvest unit was compiled with)
 #include "wh_device.h"
+#include "wh_reduce.h"
 #include "wh_host.h"
 #include "wh_hv_types.h"
 #include "wh_math.h"

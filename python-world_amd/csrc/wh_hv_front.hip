@@ -8,6 +8,7 @@
 #include "wh_tid.h"
 #include "wh_bands.h"
 #include "wh_device.h"
+#include "wh_reduce.h"
 #include "wh_host.h"
 #include "wh_hv_types.h"
 #include "wh_math.h"

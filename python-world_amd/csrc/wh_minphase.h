@@ -1,19 +1,17 @@
 // The minimum-phase chain shared by the pulse responses (wh_synthesis.hip) and the Requiem filter (wh_requiem.hip): the
 // transcendentals of its loops as real calls, and min_phase_response.  Its arithmetic may fuse a*b+c into one FP64
 // instruction (the library is built with -ffp-contract=off): the outputs are compared with the reference at tolerances.
-// Include after wh_math.h and wh_device.h (with the unit's opaque WH_TID).
+// Include after wh_math.h and the unit's opaque WH_TID (wh_tid.h).
 #pragma once
 #include <type_traits>
+#include "wh_fft.h"
 
 namespace {
 
-#ifndef WH_FT_SYNTH
-#define WH_FT_SYNTH 256
-#endif
 // Threads cooperating on one pulse / frame: 256 up to N = 1024, 512 from N = 2048 (44.1 / 48 kHz), where the 54 KB
 // of LDS per pulse leave two workgroups per CU and the thread count is the occupancy (measured 58.6 -> 50.5 ms on
 // config 5).
-constexpr int ft_syn(int n) { return n >= 2048 ? 2 * WH_FT_SYNTH : WH_FT_SYNTH; }
+constexpr int ft_syn(int n) { return n >= 2048 ? 512 : 256; }
 
 // Transcendentals of the per-pulse loop as real calls: inlined, their polynomial coefficients (64-bit literals live in
 // VGPR pairs) are loop invariants of response_kernel's pulse loop and get parked in registers across the whole body.

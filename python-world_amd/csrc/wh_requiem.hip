@@ -6,6 +6,7 @@
 #include "wh_math.h"
 #include "wh_tid.h"  // (the opaque thread index of the spectral units)
 #include "wh_device.h"
+#include "wh_fft.h"
 #include "wh_syn_types.h"
 #include "wh_minphase.h"
 
@@ -157,10 +158,7 @@ __global__ void req_hann_kernel(double* __restrict__ w, int wlen) {
 // beyond (no benchmark config decodes Requiem there).  At the north-star size (1024 x 10 s, round 6): 1 frame 23.4 + 3.2 ms
 // (nine workgroups per CU instead of six: -7 % for +50 % of the waves — the kernel is not waiting for occupancy), 2 frames
 // 25.3 + 2.0, 4 frames 25.1 + 1.2, 8 frames 27.0 + 0.9
-#ifndef WH_REQ_RUNF
-#define WH_REQ_RUNF 4
-#endif
-constexpr int req_runf(int n) { return n <= 1024 ? WH_REQ_RUNF : 1; }
+constexpr int req_runf(int n) { return n <= 1024 ? 4 : 1; }
 
 // Frame-wise minimum-phase filtering of the excitation with overlap-add (synthesisRequiem.py:74-101), WITHOUT atomics:
 // a workgroup takes a run of RUNF consecutive frames of one utterance, adds their responses — in frame order — into an
@@ -173,11 +171,8 @@ constexpr int req_runf(int n) { return n <= 1024 ? WH_REQ_RUNF : 1; }
 // the sum at the 1-based sample a_r + j, a_r = r RUNF hop + 1.  RUNF = 1 (long transforms, long hops): the row is the
 // frame's own response, written straight from the transform buffer.  Rows instead of atomics take the 1.07 GB of
 // read-modify-write traffic per 64 utterances down to a 0.33 GB row write + as much read by the gather.
-#ifndef WH_REQ_MINW
-#define WH_REQ_MINW 1
-#endif
 template <int N, int RUNF>
-__global__ __launch_bounds__(ft_syn(N), (RUNF > 1 && N <= 1024 ? WH_REQ_MINW : 1)) void req_filter_kernel(const SynUtt* __restrict__ meta, const ReqUtt* __restrict__ rq,
+__global__ __launch_bounds__(ft_syn(N), 1) void req_filter_kernel(const SynUtt* __restrict__ meta, const ReqUtt* __restrict__ rq,
                                                         const double* __restrict__ spectrogram,
                                                         const double* __restrict__ exc,
                                                         const double2* __restrict__ tw_base_arg, double* rows,

@@ -9,6 +9,7 @@
 #include <math.h>
 
 #include "wh_device.h"
+#include "wh_reduce.h"
 #include "wh_host.h"
 
 namespace {

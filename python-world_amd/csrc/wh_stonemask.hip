@@ -9,6 +9,7 @@
 //                          kernel leaves (and on all frames when its tables would not fit LDS).
 #include "wh_host.h"
 #include "wh_device.h"
+#include "wh_reduce.h"
 
 namespace {
 
@@ -175,10 +176,7 @@ __global__ __launch_bounds__(64) void stonemask_kernel(
 // paid per frame by a whole wave (32 wave-wide reductions per frame were half of the staged kernel's instructions).
 // Frames the table does not cover (windows reaching before the signal start, where the reference's rounding changes
 // sign, or f0 below the table's floor) are flagged in `todo` and taken by stonemask_kernel in a second launch.
-#ifndef WH_SM_LANES
-#define WH_SM_LANES 8
-#endif
-constexpr int kSmLanes = WH_SM_LANES;  // lanes per frame (2 / 4 / 8 / 16: 0.48 / 0.38 / 0.31 / 0.31 ms at config 2)
+constexpr int kSmLanes = 8;  // lanes per frame (2 / 4 / 8 / 16: 0.48 / 0.38 / 0.31 / 0.31 ms at config 2)
 
 template <int CTRL>
 __device__ __forceinline__ double sm_dpp(double v) {
@@ -259,10 +257,8 @@ __device__ __forceinline__ void tab_bins(wh::ckp<const double> WH_RESTRICT xu, l
   }
 }
 
-#ifndef WH_SM_MINW
-#define WH_SM_MINW 1  // (5: 96 VGPRs but 24 spilled, 0.30 -> 0.29 ms — not taken; 6: 0.76 ms)
-#endif
-__global__ __launch_bounds__(256, WH_SM_MINW) void stonemask_tab_kernel(
+// (one wave per SIMD asked for; 5: 96 VGPRs but 24 spilled, 0.30 -> 0.29 ms — not taken; 6: 0.76 ms)
+__global__ __launch_bounds__(256, 1) void stonemask_tab_kernel(
     const double* __restrict__ x, const int64_t* __restrict__ x_off, const int32_t* __restrict__ frame_utt,
     const double* __restrict__ tp, const double* __restrict__ f0_in, double* __restrict__ f0_out, double fs, int kmax,
     const double2* __restrict__ win_tab, const double* __restrict__ qtime, const double2* __restrict__ tw_base,
@@ -388,13 +384,10 @@ extern "C" int wh_stonemask(wh_ctx* ctx, void* stream, const wh_batch* b, const 
   if (int rc = wh::allow_lds(&stonemask_kernel, lds)) return rc;
   // Tabulated form first (see stonemask_tab_kernel); it needs the largest transform's twiddles in LDS.
   const uint8_t* d_only = nullptr;
-#ifndef WH_STONEMASK_TABLE
-#define WH_STONEMASK_TABLE 1
-#endif
   int tw_n = 1;
   while (tw_n < 2 * kmax + 1) tw_n <<= 1;
   tw_n <<= 1;
-  const bool use_tab = WH_STONEMASK_TABLE && tw_n <= 2048;
+  const bool use_tab = tw_n <= 2048;
   if (use_tab) {
     snprintf(key, sizeof key, "smtab:%.3f:%d", fs, kmax);
     const double2* d_wtab = nullptr;

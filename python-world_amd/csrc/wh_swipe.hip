@@ -17,6 +17,8 @@
 #include <math.h>
 
 #include "wh_device.h"
+#include "wh_fft.h"
+#include "wh_reduce.h"
 #include "wh_host.h"
 
 

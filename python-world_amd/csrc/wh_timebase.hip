@@ -14,6 +14,7 @@
 #include "wh_math.h"
 #include "wh_tid.h"  // (the opaque thread index of the spectral units)
 #include "wh_device.h"
+#include "wh_reduce.h"
 #include "wh_syn_types.h"
 
 namespace {
@@ -68,14 +69,8 @@ __global__ __launch_bounds__(256) void prep_kernel(const SynUtt* __restrict__ me
 //     repeats behind it.  There are ~17 binade crossings and ~1 tie per binade in a whole utterance, so a tile
 //     takes one pass almost always.
 // 5 ns per sample for the sequential add chain (tools/ubench/chain.hip) becomes ~0.5 ns.
-#ifndef WH_XTILE
-#define WH_XTILE 4096
-#endif
-constexpr int kXTile = WH_XTILE;
-#ifndef WH_XTHREADS
-#define WH_XTHREADS 512
-#endif
-constexpr int kXThreads = WH_XTHREADS;
+constexpr int kXTile = 4096;
+constexpr int kXThreads = 512;
 constexpr int kXPer = kXTile / kXThreads;
 constexpr int kXLds = kXTile + kXTile / kXPer;  // padded tile (xpad)
 __device__ __forceinline__ int xpad(int i) { return i + i / kXPer; }  // thread-contiguous runs of kXPer: odd stride in doubles
@@ -415,10 +410,7 @@ __global__ __launch_bounds__(256) void xs_apply_kernel(double* __restrict__ data
 // set of launches), the rest the one-workgroup-per-sequence kernel (10 s at 16 kHz is 40 tiles, a dozen of which hold a
 // binade crossing or a tie: 0.21 ms either way; 120 s at 48 kHz is 1407 tiles: 1.2 against 4.7 ms).
 // h_off: n_seg + 1 offsets into d_data (HOST).
-#ifndef WH_XS_MIN_TILES
-#define WH_XS_MIN_TILES 64
-#endif
-constexpr int kXsMinTiles = WH_XS_MIN_TILES;
+constexpr int kXsMinTiles = 64;
 }  // namespace
 int wh::exact_cumsum_segments(wh_ctx* ctx, hipStream_t st, double* d_data, const int64_t* h_off, int n_seg) {
   std::vector<int64_t> s_pairs, l_pairs, tb{0};
@@ -463,10 +455,7 @@ namespace {
 //   pulse_finish_kernel : one workgroup per utterance: fractional shifts and the noise-stream offsets
 //                         (exclusive prefix sum of max(3, noise_size), synthesis.py:65).
 constexpr int kPTile = 1024;
-#ifndef WH_PFINISH
-#define WH_PFINISH 1024  // threads of pulse_finish_kernel (one workgroup per utterance); the sanitizer build takes 256
-#endif
-constexpr int kPFinish = WH_PFINISH;
+constexpr int kPFinish = 1024;  // threads of pulse_finish_kernel (one workgroup per utterance)
 
 
 __global__ __launch_bounds__(256) void pulse_mark_kernel(const SynUtt* __restrict__ meta, const double* __restrict__ phase,

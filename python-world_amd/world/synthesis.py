@@ -77,7 +77,7 @@ def synthesis_device(rt, batch, tp_d, f0_d, vuv_d, spec_d, ap_d, fs, fft_size, n
     return y, y_off
 
 
-_PHILOX_SEED_MUL, _PHILOX_UTT_MUL = 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03  # philox_key (csrc/wh_synthesis.hip)
+_PHILOX_SEED_MUL, _PHILOX_UTT_MUL = 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03  # philox_key (csrc/wh_philox.h)
 
 
 def philox_seed_for_offset(seed, first_utt):

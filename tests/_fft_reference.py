@@ -1,6 +1,6 @@
 """The reference of tests/test_hip_fft_engine.py: a radix-2 decimation-in-time FFT in np.longdouble (plain NumPy, no GPU),
 forward, inverse (unnormalised, like the kernels') and the real wrappers; and a restatement of wh::FftRadix
-(csrc/wh_device.h) that gives the passes of the plan the kernels run at (N, NT, MAXR).
+(csrc/wh_fft.h) that gives the passes of the plan the kernels run at (N, NT, MAXR).
 
 An 80-bit x86 long double is assumed (eps 1.08e-19), as everywhere else in the suite that uses np.longdouble: the
 reference's own error, ~2.5e-17 relative at N = 256, then lies a factor 40 under the 1e-15 the transforms are held to."""
@@ -116,7 +116,7 @@ def dft_column(n, p, inverse=False):
 
 
 def plan(n, nt, maxr=8):
-    """The radices of fft_lds<n, .., nt, .., maxr>'s passes: wh::FftRadix (csrc/wh_device.h) restated."""
+    """The radices of fft_lds<n, .., nt, .., maxr>'s passes: wh::FftRadix (csrc/wh_fft.h) restated."""
     out = []
     ns = 1
     while ns < n:

@@ -1,7 +1,7 @@
 """Helper of tests/test_hip_fft_engine.py (test d).  wh_fft_probe lives in wh_api.hip, which is compiled without
 floating-point contraction; wh_fft_engine_probe lives in wh_fft_probe.hip, compiled like the spectral kernels, where the
 compiler fuses a radix-8 butterfly's h * (x + y) into the additions behind it.  "The same plan, layout and twiddles: the same
-bits" (wh_device.h) can only be observed between the two hooks in a build that compiles both alike: the NOCONTRACT variant,
+bits" (wh_fft.h) can only be observed between the two hooks in a build that compiles both alike: the NOCONTRACT variant,
 libworld_hip.so with wh_fft_probe.hip at -ffp-contract=off (tools/build_variants.py; never shipped).  As a script (WH_LIB =
 that variant) it runs both hooks on the same 37 transforms of 512 points and prints one JSON line."""
 import json

@@ -1,5 +1,5 @@
 """CPU: the long-double reference of tests/test_hip_fft_engine.py checked against the DFT sum itself, the restated radix
-plan against the two plans csrc/wh_device.h states in its comments, and a tripwire over the transforms' call sites."""
+plan against the two plans csrc/wh_fft.h states in its comments, and a tripwire over the transforms' call sites."""
 import glob
 import os
 import re
@@ -50,7 +50,7 @@ def test_twiddles_are_exact_on_the_axes_and_symmetric():
 
 
 def test_restated_radix_plan():
-    assert R.plan(512, 64) == [8, 8, 8]            # wh_device.h: "fft_lds<N, INV, GT> runs 8-8-8 (GT <= 128 at N = 512)"
+    assert R.plan(512, 64) == [8, 8, 8]            # wh_fft.h: "fft_lds<N, INV, GT> runs 8-8-8 (GT <= 128 at N = 512)"
     assert R.plan(512, 128) == [8, 8, 8]
     assert R.plan(512, 256) == [4, 4, 4, 4, 2]     # "a 256-thread group's 4-4-4-4-2 plan"
     assert R.plan(2048, 256) == [8, 8, 8, 4]       # "radix 8 needs 4 passes for 2048 points where radix 4 needs 6"
@@ -61,7 +61,7 @@ def test_restated_radix_plan():
     assert R.TWIDDLE_ENTRIES == 2 * 32768 + 8191 + 3 * 4095 + 7 * 2047
 
 
-# (file, function) -> call sites in csrc/ (comments stripped; wh_device.h itself, where the transforms are defined and call
+# (file, function) -> call sites in csrc/ (comments stripped; wh_fft.h itself, where the transforms are defined and call
 # each other, and the probe are left out)
 CALL_SITES = {
     ("wh_api.hip", "fft_lds_wave"): 2,
@@ -84,7 +84,7 @@ def test_call_site_tripwire():
     found = {}
     for path in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h"))):
         name = os.path.basename(path)
-        if name in ("wh_device.h", "wh_fft_probe.hip"):
+        if name in ("wh_fft.h", "wh_fft_probe.hip"):
             continue
         with open(path) as f:
             text = f.read()

@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-BOUNDS_TUS = ("wh_api", "wh_cheaptrick", "wh_stonemask", "wh_harvest", "wh_hv_front", "wh_hv_refine", "wh_hv_contour", "wh_timebase", "wh_synthesis", "wh_requiem", "wh_d4c",
+BOUNDS_TUS = ("wh_api", "wh_cheaptrick", "wh_stonemask", "wh_harvest", "wh_hv_front", "wh_hv_refine", "wh_hv_contour", "wh_timebase", "wh_synthesis", "wh_peak", "wh_requiem", "wh_d4c",
               "wh_apbands", "wh_d4c_probe", "wh_fft_probe", "wh_spectral_probe")
 VARIANT = os.path.join(ROOT, "python-world_amd", "lib", "variants", "libworld_hip_bounds.so")
 

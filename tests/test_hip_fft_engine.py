@@ -1,4 +1,4 @@
-"""GPU: the shared transform engine of csrc/wh_device.h (fft_lds, fft_lds_from_regs, rfft_lds, irfft_lds), through
+"""GPU: the shared transform engine of csrc/wh_fft.h (fft_lds, fft_lds_from_regs, rfft_lds, irfft_lds), through
 wh_fft_engine_probe, at every (N, NT, SNT, MAXR, direction) shape the kernels instantiate, against a long-double FFT
 (tests/_fft_reference.py); and the twiddle block the transforms read, through wh_twiddle_read.
 
@@ -271,7 +271,7 @@ def test_c_inverse_real_ignores_dc_and_nyquist_phase_and_round_trips(s):
     clean[:, -1] = 0.0
     assert np.any(im[:, 0] != 0.0) and np.any(im[:, -1] != 0.0)
     a, b = _probe(s, _pack(re, im)), _probe(s, _pack(re, clean))
-    assert np.array_equal(a, b)  # "imaginary parts of the DC / Nyquist bins are ignored" (wh_device.h)
+    assert np.array_equal(a, b)  # "imaginary parts of the DC / Nyquist bins are ignored" (wh_fft.h)
     # irfft(rfft(x)) / n = x, through the forward shape of the same threads
     fwd = (2,) + tuple(s[1:5]) + (0,)
     assert fwd in SHAPES

@@ -368,10 +368,10 @@ def test_encoding_dict_materialises_on_read_and_remembers_it():
 def test_philox_seed_for_offset_rekeys_the_utterance_streams():
     """World.decode_batch renders a large batch in consecutive parts; utterance u of a part that starts at utterance
     `base` must draw the noise of utterance base + u of the whole batch.  The device keys a stream with
-    seed * A + u * B + 1 mod 2**64 (philox_key, csrc/wh_synthesis.hip): the shifted seed solves that for every u."""
+    seed * A + u * B + 1 mod 2**64 (philox_key, csrc/wh_philox.h): the shifted seed solves that for every u."""
     from world.synthesis import _PHILOX_SEED_MUL as A, _PHILOX_UTT_MUL as B, philox_seed_for_offset
 
-    src = open(os.path.join(os.path.dirname(__file__), "..", "python-world_amd", "csrc", "wh_synthesis.hip")).read()
+    src = open(os.path.join(os.path.dirname(__file__), "..", "python-world_amd", "csrc", "wh_philox.h")).read()
     assert "return seed * 0x%Xull + u * 0x%Xull + 1;" % (A, B) in src  # the constants are the kernel's
     m = 1 << 64
     key = lambda seed, u: (seed * A + u * B + 1) % m  # noqa: E731

@@ -2,7 +2,7 @@
 """Build tuning variants of libworld_hip.so next to the shipped one (python-world_amd/lib/variants/): only the
 translation units whose flags differ are recompiled, the rest is linked from python-world_amd/build/*.o.
 
-    tools/build_variants.py name=wh_d4c:-DWH_D4C_STAGE_TIMER other=wh_synthesis:-DWH_RESP_RUN=8 ...
+    tools/build_variants.py name=wh_d4c:-DWH_D4C_STAGE_TIMER other=wh_synthesis:-DWH_RESP_STAGE_TIMER ...
 
 Select one at run time with WH_LIB=python-world_amd/lib/variants/libworld_hip_<name>.so (world/_hip.py)."""
 import os

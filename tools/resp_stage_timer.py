@@ -33,7 +33,8 @@ v = np.array(list(buf), dtype=np.float64)
 # slot 5: from the pulse's start to the logs; slot 0: from there to the chains (with the wave roles of the 16 kHz shape the
 # noise run and its mean are no longer here: the run is generated under the chains' first transform, and the mean
 # is taken in front of the convolution, slot 3).  The chains' stage by the kind of pulse: slot 2 voiced (two chains side by
-# side), slot 6 unvoiced (one chain), slot 7 two unvoiced pulses side by side (-DWH_RESP_PAIR=1).
+# side), slot 6 unvoiced (one chain), slot 7 two unvoiced pulses side by side (the 16 kHz shape).
+# The slots are RespStage of csrc/wh_resp_types.h.
 names = {5: "setup: pulse look-up, spectral rows, interpolation, logs", 0: "setup: noise run + mean in front of the chains",
          2: "minimum-phase chains, voiced pulses", 6: "minimum-phase chains, unvoiced pulses one by one",
          7: "minimum-phase chains, unvoiced pulses in pairs", 3: "response reorder + noise convolution",
@@ -47,7 +48,7 @@ print("pulses %d: voiced %d, unvoiced with vuv == 0 %d, unvoiced by the aperiodi
 if n_pairs:
     print("pairs taken %d (%d of the %d vuv == 0 pulses)" % (n_pairs, 2 * n_pairs, n_unv0))
 else:
-    # (-DWH_RESP_PAIR=0) a pulse has a partner when its successor in the run has vuv == 0 too, the noise is the device
+    # (the shapes without pairs: resp_pairs<N>() is false) a pulse has a partner when its successor in the run has vuv == 0 too, the noise is the device
     # stream's and both runs fit nz together; pairs are disjoint, so a stretch of n such pulses in a row makes about n / 2
     per_pulse = v[6] / max(1, n_unv0 + n_unv_rows)
     print("vuv == 0 pulses whose successor in the run can share the chains with them: %d" % n_partner)

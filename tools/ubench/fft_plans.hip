@@ -1,10 +1,11 @@
-// Micro-benchmark of the in-LDS FP64 transform engine (wh_device.h: fft_lds / fft_lds_from_regs) at the shapes config 2's
+// Micro-benchmark of the in-LDS FP64 transform engine (wh_fft.h: fft_lds / fft_lds_from_regs) at the shapes config 2's
 // three heavy kernels run it: the same header, the same context twiddle table, config 2's count of transforms (128 k),
 // device-event timing, and every bin of 16 of the transforms checked against a host FP64 DFT.
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off fft_plans.hip -o fft_plans.bin && ./fft_plans.bin
 //
-// -DFFT_HEADER='"path/wh_device.h"' times another revision of the engine (an A/B of two builds of this file).
+// -DFFT_HEADER='"path/wh_fft.h"' times another revision of the engine (an A/B of two builds of this file; wh_device.h
+// for a revision from before the engine had a header of its own).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -12,7 +13,7 @@
 #include <vector>
 
 #ifndef FFT_HEADER
-#define FFT_HEADER "../../python-world_amd/csrc/wh_device.h"
+#define FFT_HEADER "../../python-world_amd/csrc/wh_fft.h"
 #endif
 #include FFT_HEADER
 

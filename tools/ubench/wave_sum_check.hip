@@ -1,9 +1,9 @@
 // Does the DPP form of the 64-lane FP64 sum (quad_perm / row mirrors inside rows of 16, row_bcast:15 and :31 across
-// rows, total in lane 63) assemble for gfx950 and give the sum?  (settles wh::wave_sum in wh_device.h)
+// rows, total in lane 63) assemble for gfx950 and give the sum?  (settles wh::wave_sum in wh_reduce.h)
 // hipcc --offload-arch=gfx950 -O2 wave_sum_check.hip -o wave_sum_check.bin && ./wave_sum_check.bin
 #include <hip/hip_runtime.h>
 #include <cstdio>
-#include "../../python-world_amd/csrc/wh_device.h"
+#include "../../python-world_amd/csrc/wh_reduce.h"
 __global__ void k(const double* in, double* out) {
   const double v = in[threadIdx.x];
   out[threadIdx.x] = wh::wave_sum(v);
