@@ -501,6 +501,44 @@ int wh_delta_features(wh_ctx* ctx, void* stream, const wh_batch* b, const double
 int wh_mlpg(wh_ctx* ctx, void* stream, const wh_batch* b, const double* mean, int64_t ldm, const double* var, int64_t ldv,
             int d, int n_win, int half, const double* h_win, double* out, int64_t ldo, double* pivots_out);
 
+/* ---- Joint-density Gaussian mixtures for voice conversion (no counterpart in the reference's library) ------------------ */
+/* The frame-proportional parts of EM on joint vectors and of the conversion (Toda, Black and Tokuda 2007; DESIGN section
+ * 16; tests/_gmm_reference.py is the same contract in NumPy).  Every matrix is row-major FP64 on the DEVICE; rows of x have
+ * a stride ldx >= their width.  1 <= d <= 160, 1 <= M <= 64; a limit exceeded, a stride below the row width or a null
+ * pointer where one is needed fails before anything is launched; n_rows == 0 is no error and launches nothing.  The three
+ * products run on the FP64 matrix cores, so a sum's order and fusing are not part of the contract: results are held to
+ * error bounds derived from the operands, and are exact where every partial sum is.  A row's result never depends on the
+ * other rows of the call; non-finite input flows through as NaN or +-inf, and no index or trip count depends on a value.
+ *   wh_gmm_estep:  mu [M][d], whiten [M][d][d] = W_m = L_m^-T (upper triangular; the lower triangle is not read above
+ *     the 16 x 16 blocks of the diagonal and must hold zeros), logc [M] = log w_m - sum log diag L_m - (d/2) log 2 pi.
+ *       z = (x_n - mu_m) W_m;  ll[n][m] = logc[m] - 0.5 sum_j z_j^2;
+ *       mx = max_m ll;  s = sum over m ascending of exp(ll[n][m] - mx);  rowll[n] = mx + log s;
+ *       gamma[n][m] = exp(ll[n][m] - mx) / s;  best[n] = the smallest m that attains mx (int32).
+ *     exp and log are the device library's (<= 1 ulp).  ll (row stride ldl >= M), gamma (ldg >= M), rowll and best may
+ *     each be NULL.
+ *   wh_gmm_stats:  gamma [n_rows][M] with stride ldg, mu [M][d] the centre of each component;
+ *       s0[m] = sum_n gamma;  s1[m][i] = sum_n gamma (x_i - mu_mi);  s2[m][i][j] = sum_n gamma (x_i - mu_mi)(x_j - mu_mj).
+ *     Both triangles of s2 are written and agree bit for bit.  The rows are summed in consecutive runs of 4096 whose
+ *     partial results ([run][m][d+1][d+1], wh_gmm_workspace_bytes(n_rows, d, M) bytes of the context's scratch) are
+ *     added in ascending order: no atomics, the same input gives the same bits on every run.
+ *   wh_gmm_convert:  x [n_rows][dx], mu_x [M][dx], a [M][dx][dy] = A_m = Sigma_xx^-1 Sigma_xy, mu_y [M][dy]; dx, dy >= 1,
+ *     dx + dy <= 160.  Exactly one of best (int32 [n_rows]) and g ([n_rows][M], stride ldg) is given:
+ *       best:  out[n] = mu_y[m] + (x_n - mu_x[m]) A_m  for m = best[n]  (a value outside [0, M) gives a row of zeros);
+ *       g:     out[n] = sum over m ascending of g[n][m] * (mu_y[m] + (x_n - mu_x[m]) A_m)   (the MMSE conversion),
+ *              evaluated as one accumulation of (g[n][m] (x_n - mu_x[m])) A_m over all m and k with sum_m g[n][m] mu_y[m]
+ *              behind it.
+ *     out has the row stride ldo >= dy and must not overlap an input.
+ *   wh_gmm_workspace_bytes: host only; -1 for arguments outside the limits. */
+int wh_gmm_estep(wh_ctx* ctx, void* stream, const double* x, int64_t n_rows, int64_t ldx, int d, int M, const double* mu,
+                 const double* whiten, const double* logc, double* ll, int64_t ldl, double* gamma, int64_t ldg,
+                 double* rowll, int32_t* best);
+int wh_gmm_stats(wh_ctx* ctx, void* stream, const double* x, int64_t n_rows, int64_t ldx, int d, int M, const double* gamma,
+                 int64_t ldg, const double* mu, double* s0, double* s1, double* s2);
+int wh_gmm_convert(wh_ctx* ctx, void* stream, const double* x, int64_t n_rows, int64_t ldx, int dx, int dy, int M,
+                   const double* mu_x, const double* a, const double* mu_y, const int32_t* best, const double* g,
+                   int64_t ldg, double* out, int64_t ldo);
+int64_t wh_gmm_workspace_bytes(int64_t n_rows, int d, int M);
+
 /* ---- 16-bit PCM at the batch boundary (the reference's WAV usage: example/prosody.py:12-13,57) ---------------------- */
 /* x[i] = pcm[i] / (2^15 - 1); pcm[i] = int16(trunc(y[i] * 2^15)) (low 16 bits, like NumPy's astype on the reference's
  * platform).  DEVICE pointers: the 2-byte samples cross PCIe instead of the 8-byte ones. */

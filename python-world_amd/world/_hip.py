@@ -98,6 +98,13 @@ SIGNATURES = {
                                  ctypes.c_int64]),
     "wh_mlpg": (_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _int, _int, _int, ctypes.POINTER(_dbl), _vp,
                        ctypes.c_int64, _vp]),
+    "wh_gmm_estep": (_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _int, _int, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp,
+                            ctypes.c_int64, _vp, _vp]),
+    "wh_gmm_stats": (_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _int, _int, _vp, ctypes.c_int64, _vp, _vp, _vp,
+                            _vp]),
+    "wh_gmm_convert": (_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp,
+                              ctypes.c_int64, _vp, ctypes.c_int64]),
+    "wh_gmm_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, _int, _int]),
     "wh_pcm16_to_f64": (_int, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
     "wh_f64_to_pcm16": (_int, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
     "wh_swipe": (_int, [_vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp]),

@@ -1,0 +1,434 @@
+"""Joint-density Gaussian mixture voice conversion (Toda, Black and Tokuda 2007): the model between align() /
+dynamic_features() on one side and mlpg_device() on the other.  A mixture with full covariances is fitted by EM on the
+joint rows [x; y] of two aligned speakers; a source row is converted by the posterior over the components under the
+marginal of x, the conditional mean and variance of y given x for the most likely component, and MLPG over the result.
+
+The frame-proportional work — the whitening product of the E-step, the weighted outer-product sums of the statistics,
+the affine map of the conversion — runs on the FP64 matrix cores behind wh_gmm_estep / wh_gmm_stats / wh_gmm_convert
+(csrc/wh_gmm.hip; contract in include/world_hip.h, DESIGN section 16, and in NumPy in tests/_gmm_reference.py).  The
+per-component algebra (a d x d Cholesky factor per component, its inverse, the regression matrices) is tiny and is NumPy
+on the host.  Neither scipy nor scikit-learn is imported.
+
+The argument checks, the tables and the workspace grouping are host code and need neither the library nor a GPU."""
+import numpy as np
+
+from . import _hip
+from .dynamics import HTS_WINDOWS, check_windows
+
+# the kernels' limits and tiling (csrc/wh_gmm.hip: kGmmMaxD, kGmmMaxM, kGmmRowTile, kGmmSplitRows); the tests put their
+# shapes around the last two, and tests/test_gmm_host.py holds the two files together
+MAX_D = 160
+MAX_M = 64
+ROW_TILE = 128
+SPLIT_ROWS = 4096
+DEFAULT_MAX_WORKSPACE_BYTES = 4 << 30
+CONVERT_MODES = ("mlpg", "mmse", "frame")
+CONVERSION_WINDOWS = HTS_WINDOWS[:2]  # static + delta: 39 + 39 coefficients per speaker, a joint vector of 156
+
+
+# ---- host ------------------------------------------------------------------------------------------------------------
+def check_limits(d, m, where="gmm"):
+    if not 1 <= int(d) <= MAX_D:
+        raise ValueError("%s: rows of %d columns; the kernels take 1 .. %d" % (where, d, MAX_D))
+    if not 1 <= int(m) <= MAX_M:
+        raise ValueError("%s: %d components; the kernels take 1 .. %d" % (where, m, MAX_M))
+
+
+def workspace_bytes(n_rows, d, m):
+    """What wh_gmm_stats takes of the context's scratch for ``n_rows`` rows: one (d + 1) x (d + 1) partial result per
+    component and run of SPLIT_ROWS rows (3.2 GB for 2 049 024 rows, d = 156, M = 32)."""
+    check_limits(d, m, "workspace_bytes")
+    if n_rows < 0:
+        raise ValueError("workspace_bytes: n_rows must be >= 0")
+    return 8 * ((int(n_rows) + SPLIT_ROWS - 1) // SPLIT_ROWS) * int(m) * (int(d) + 1) ** 2
+
+
+def plan_row_groups(n_rows, d, m, max_workspace_bytes=DEFAULT_MAX_WORKSPACE_BYTES):
+    """Consecutive row ranges [r0, r1) per wh_gmm_stats call: as many whole runs of SPLIT_ROWS rows as keep the partial
+    results under ``max_workspace_bytes``, at least one run."""
+    per_run = workspace_bytes(SPLIT_ROWS, d, m)
+    rows = max(1, int(max_workspace_bytes) // per_run) * SPLIT_ROWS
+    return [(r0, min(int(n_rows), r0 + rows)) for r0 in range(0, int(n_rows), rows)]
+
+
+def cholesky_tables(weights, means, covariances, where="gmm"):
+    """(whiten [M][d][d], logc [M]) of a mixture: L_m by numpy.linalg.cholesky, W_m = L_m^-T by substitution (upper
+    triangular, the lower triangle zeros), logc[m] = log w_m - sum log diag L_m - (d / 2) log 2 pi.  ValueError naming the
+    component whose covariance is not symmetric positive definite."""
+    w, mu, cov = (np.asarray(a, dtype=np.float64) for a in (weights, means, covariances))
+    m, d = mu.shape
+    whiten, logc = np.zeros((m, d, d)), np.zeros(m)
+    for k in range(m):
+        if not np.all(np.isfinite(cov[k])) or not np.array_equal(cov[k], cov[k].T):
+            raise ValueError("%s: the covariance of component %d is not symmetric and finite" % (where, k))
+        try:
+            low = np.linalg.cholesky(cov[k])
+        except np.linalg.LinAlgError:
+            raise ValueError("%s: the covariance of component %d is not positive definite" % (where, k))
+        inv = np.zeros((d, d))  # L^-1, row by row: L inv = I
+        for i in range(d):
+            row = -(low[i, :i] @ inv[:i])
+            row[i] += 1.0
+            inv[i] = row / low[i, i]
+        whiten[k] = np.triu(inv.T)
+        logc[k] = np.log(w[k]) - np.sum(np.log(np.diag(low))) - 0.5 * d * np.log(2.0 * np.pi)
+    return whiten, logc
+
+
+def m_step(means, s0, s1, s2, reg_covar):
+    """The host M-step from statistics centred at ``means``: nk = s0 + 10 eps, delta = s1 / nk, mu += delta,
+    Sigma = s2 / nk - delta delta' + reg_covar I, w = nk / sum nk.  Returns (weights, means, covariances)."""
+    nk = np.asarray(s0, dtype=np.float64) + 10.0 * np.finfo(np.float64).eps
+    delta = s1 / nk[:, None]
+    d = means.shape[1]
+    cov = s2 / nk[:, None, None] - delta[:, :, None] * delta[:, None, :] + reg_covar * np.eye(d)[None]
+    return nk / np.sum(nk), means + delta, cov
+
+
+class JointGMM:
+    """A mixture over joint rows [x; y]: weights [M], means [M][D], covariances [M][D][D] (host float64), the first
+    ``dx`` columns being the source's."""
+
+    def __init__(self, weights, means, covariances, dx):
+        self.weights = np.ascontiguousarray(weights, dtype=np.float64)
+        self.means = np.ascontiguousarray(means, dtype=np.float64)
+        self.covariances = np.ascontiguousarray(covariances, dtype=np.float64)
+        if self.means.ndim != 2:
+            raise ValueError("JointGMM: means must be [M][D], got shape %s" % (self.means.shape,))
+        m, d = self.means.shape
+        check_limits(d, m, "JointGMM")
+        if self.weights.shape != (m,) or self.covariances.shape != (m, d, d):
+            raise ValueError("JointGMM: weights must be [%d] and covariances [%d][%d][%d], got %s and %s"
+                             % (m, m, d, d, self.weights.shape, self.covariances.shape))
+        if isinstance(dx, bool) or int(dx) != dx or not 1 <= dx <= d - 1:
+            raise ValueError("JointGMM: dx must be an integer in [1, %d], got %r" % (d - 1, dx))
+        if not np.all(self.weights > 0.0) or not np.all(np.isfinite(self.weights)) or not np.all(np.isfinite(self.means)):
+            raise ValueError("JointGMM: weights must be positive and finite, means finite")
+        self.dx = int(dx)
+        self._host = None
+        self._dev = {}
+        self.host_tables()  # (raises for a covariance that is not symmetric positive definite)
+
+    n_components = property(lambda self: self.means.shape[0])
+    dim = property(lambda self: self.means.shape[1])
+    dy = property(lambda self: self.means.shape[1] - self.dx)
+
+    def marginal_x(self):
+        """(weights, means [M][dx], covariances [M][dx][dx]) of the source columns."""
+        dx = self.dx
+        return self.weights, np.ascontiguousarray(self.means[:, :dx]), np.ascontiguousarray(self.covariances[:, :dx, :dx])
+
+    def host_tables(self):
+        """The tables the kernels take, NumPy: 'whiten' / 'logc' of the joint mixture, 'whiten_x' / 'logc_x' of the
+        marginal of x, 'a' [M][dx][dy] = Sigma_xx^-1 Sigma_xy, 'mu_x', 'mu_y', and 'cvar' [M][dy], the diagonal of
+        Sigma_yy - Sigma_yx Sigma_xx^-1 Sigma_xy."""
+        if self._host is None:
+            dx = self.dx
+            whiten, logc = cholesky_tables(self.weights, self.means, self.covariances, "JointGMM")
+            wx, mux, cxx = self.marginal_x()
+            whiten_x, logc_x = cholesky_tables(wx, mux, cxx, "JointGMM")
+            cxy = self.covariances[:, :dx, dx:]
+            half = np.einsum("mki,mkj->mij", whiten_x, cxy)  # W_x' Sigma_xy = L_x^-1 Sigma_xy
+            a = np.einsum("mik,mkj->mij", whiten_x, half)
+            cvar = np.einsum("mii->mi", self.covariances[:, dx:, dx:]) - np.sum(half * half, axis=1)
+            self._host = {"whiten": whiten, "logc": logc, "whiten_x": whiten_x, "logc_x": logc_x,
+                          "a": np.ascontiguousarray(a), "mu_x": mux, "mu_y": np.ascontiguousarray(self.means[:, dx:]),
+                          "cvar": np.ascontiguousarray(cvar), "mu": self.means}
+        return self._host
+
+    def prepared(self, rt):
+        """host_tables() resident on ``rt``'s device (uploaded once per runtime)."""
+        key = (rt.index, rt.lane)
+        if key not in self._dev:
+            with rt.lock, rt.on_stream():
+                self._dev[key] = {k: rt.to_device(v) for k, v in self.host_tables().items()}
+        return self._dev[key]
+
+    def save_npz(self, path):
+        np.savez(path, weights=self.weights, means=self.means, covariances=self.covariances, dx=np.asarray(self.dx))
+
+    @classmethod
+    def load_npz(cls, path):
+        with np.load(path) as z:
+            return cls(z["weights"], z["means"], z["covariances"], int(z["dx"]))
+
+
+def check_convert_args(x_shape, frames, gmm, mode, windows, where="convert"):
+    """ValueError for what convert_device cannot take.  Returns (win, half, d_y): the windows and the static columns of
+    the target."""
+    if mode not in CONVERT_MODES:
+        raise ValueError("%s: mode must be one of %s, got %r" % (where, CONVERT_MODES, mode))
+    win, half = check_windows(windows, where)
+    if len(x_shape) != 2 or int(x_shape[0]) != frames:
+        raise ValueError("%s: x must be [%d frames][%d], got %s" % (where, frames, gmm.dx, tuple(x_shape)))
+    n_win = len(win)
+    if int(x_shape[1]) != gmm.dx or gmm.dx % n_win or gmm.dy % n_win:
+        raise ValueError("%s: rows of %d columns and a model of %d + %d columns do not hold %d windows each"
+                         % (where, int(x_shape[1]), gmm.dx, gmm.dy, n_win))
+    return win, half, gmm.dy // n_win
+
+
+# ---- device: the three entries on tensors ----------------------------------------------------------------------------
+def _rows(rt, name, t, width, where):
+    if t.dim() != 2 or t.dtype != rt.torch.float64 or t.stride(1) != 1 or (width is not None and int(t.shape[1]) != width):
+        raise ValueError("%s: %s must be a float64 [rows][%s] tensor with unit column stride, got %s %s strides %s"
+                         % (where, name, "d" if width is None else width, t.dtype, tuple(t.shape), tuple(t.stride())))
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def estep_device(rt, x, mu, whiten, logc, want=("gamma", "rowll", "best")):
+    """wh_gmm_estep on device tensors: x [n][d] (row stride free), mu [M][d], whiten [M][d][d], logc [M] (contiguous).
+    Returns a dict of the outputs named in ``want`` ('ll', 'gamma', 'rowll', 'best')."""
+    m, d = int(mu.shape[0]), int(mu.shape[1])
+    check_limits(d, m, "estep")
+    ldx = _rows(rt, "x", x, d, "estep")
+    n = int(x.shape[0])
+    with rt.lock, rt.on_stream():
+        out = {k: rt.empty((n, m)) for k in ("ll", "gamma") if k in want}
+        if "rowll" in want:
+            out["rowll"] = rt.empty((n,))
+        if "best" in want:
+            out["best"] = rt.empty((n,), rt.torch.int32)
+        _hip.check(rt.lib.wh_gmm_estep(rt.ctx, rt.stream(), rt.ptr(x), n, ldx, d, m, rt.ptr(mu), rt.ptr(whiten), rt.ptr(logc),
+                                       rt.ptr(out.get("ll")), m, rt.ptr(out.get("gamma")), m, rt.ptr(out.get("rowll")),
+                                       rt.ptr(out.get("best"))))
+    return out
+
+
+def stats_device(rt, x, gamma, mu, max_workspace_bytes=DEFAULT_MAX_WORKSPACE_BYTES):
+    """wh_gmm_stats on device tensors, the rows handed over in the groups of plan_row_groups and the groups' results
+    added on the device in group order: (s0 [M], s1 [M][d], s2 [M][d][d])."""
+    m, d = int(mu.shape[0]), int(mu.shape[1])
+    check_limits(d, m, "stats")
+    ldx, ldg = _rows(rt, "x", x, d, "stats"), _rows(rt, "gamma", gamma, m, "stats")
+    n = int(x.shape[0])
+    if int(gamma.shape[0]) != n:
+        raise ValueError("stats: %d rows of x against %d of gamma" % (n, int(gamma.shape[0])))
+    with rt.lock, rt.on_stream():
+        total = None
+        for r0, r1 in plan_row_groups(n, d, m, max_workspace_bytes):
+            part = (rt.empty((m,)), rt.empty((m, d)), rt.empty((m, d, d)))
+            _hip.check(rt.lib.wh_gmm_stats(rt.ctx, rt.stream(), rt.ptr(x[r0:r1]), r1 - r0, ldx, d, m, rt.ptr(gamma[r0:r1]), ldg,
+                                           rt.ptr(mu), rt.ptr(part[0]), rt.ptr(part[1]), rt.ptr(part[2])))
+            if total is None:
+                total = part
+            else:
+                for t, p in zip(total, part):
+                    t += p
+        if total is None:
+            total = (rt.zeros((m,)), rt.zeros((m, d)), rt.zeros((m, d, d)))
+    return total
+
+
+def convert_rows_device(rt, x, mu_x, a, mu_y, best=None, g=None):
+    """wh_gmm_convert on device tensors: out [n][dy]."""
+    m, dx, dy = int(a.shape[0]), int(a.shape[1]), int(a.shape[2])
+    check_limits(dx + dy, m, "convert")
+    if (best is None) == (g is None):
+        raise ValueError("convert: exactly one of best and g must be given")
+    ldx = _rows(rt, "x", x, dx, "convert")
+    ldg = _rows(rt, "g", g, m, "convert") if g is not None else 0
+    n = int(x.shape[0])
+    with rt.lock, rt.on_stream():
+        out = rt.empty((n, dy))
+        _hip.check(rt.lib.wh_gmm_convert(rt.ctx, rt.stream(), rt.ptr(x), n, ldx, dx, dy, m, rt.ptr(mu_x), rt.ptr(a),
+                                         rt.ptr(mu_y), rt.ptr(best), rt.ptr(g), ldg, rt.ptr(out), dy))
+    return out
+
+
+# ---- device: the model -----------------------------------------------------------------------------------------------
+def posteriors_device(rt, x, gmm):
+    """(gamma [n][M], rowll [n], best [n] int32) of rows x under ``gmm``: under the joint mixture for rows of D columns,
+    under the marginal of x for rows of dx columns."""
+    t = gmm.prepared(rt)
+    if x.dim() == 2 and int(x.shape[1]) == gmm.dx:
+        o = estep_device(rt, x, t["mu_x"], t["whiten_x"], t["logc_x"])
+    elif x.dim() == 2 and int(x.shape[1]) == gmm.dim:
+        o = estep_device(rt, x, t["mu"], t["whiten"], t["logc"])
+    else:
+        raise ValueError("posteriors: x must be [rows][%d] (the source columns) or [rows][%d] (joint rows), got %s"
+                         % (gmm.dx, gmm.dim, tuple(x.shape)))
+    return o["gamma"], o["rowll"], o["best"]
+
+
+def fit_device(rt, z, dx, n_components, n_iter, reg_covar=1e-6, init=None, seed=0,
+               max_workspace_bytes=DEFAULT_MAX_WORKSPACE_BYTES):
+    """EM with full covariances on the joint rows z [n][D] (float64 device tensor): (JointGMM, history), history[i] the
+    mean log-likelihood per row under the parameters iteration i started from.  ``init``: a JointGMM, or None — every
+    choice made on the host from numpy.random.default_rng(seed): the means are ``n_components`` distinct rows of z, every
+    covariance the global covariance + reg_covar I, the weights equal.  One iteration is wh_gmm_estep (gamma and rowll),
+    wh_gmm_stats centred at the current means, a download of s0, s1, s2 and m_step on the host."""
+    if z.dim() != 2:
+        raise ValueError("fit: z must be [rows][D], got shape %s" % (tuple(z.shape),))
+    n, d = int(z.shape[0]), int(z.shape[1])
+    m = int(n_components)
+    check_limits(d, m, "fit")
+    if isinstance(dx, bool) or int(dx) != dx or not 1 <= dx <= d - 1:
+        raise ValueError("fit: dx must be an integer in [1, %d], got %r" % (d - 1, dx))
+    if n < m or n < 2:
+        raise ValueError("fit: %d rows for %d components" % (n, m))
+    if int(n_iter) < 0 or not reg_covar >= 0.0:
+        raise ValueError("fit: n_iter and reg_covar must be >= 0")
+    _rows(rt, "z", z, d, "fit")
+    torch = rt.torch
+    with rt.lock, rt.on_stream():
+        if init is not None:
+            if init.dim != d or init.n_components != m or init.dx != dx:
+                raise ValueError("fit: init is a model of %d components over %d + %d columns" % (init.n_components, init.dx, init.dy))
+            w, mu, cov = init.weights, init.means, init.covariances
+        else:
+            rng = np.random.default_rng(seed)
+            pick = np.sort(rng.choice(n, size=m, replace=False))
+            mu = z.index_select(0, torch.from_numpy(pick).to(rt.device)).cpu().numpy()
+            centre = rt.to_device(mu[:1])
+            s0, s1, s2 = (t.cpu().numpy() for t in stats_device(rt, z, rt.torch.ones((n, 1), dtype=torch.float64, device=rt.device),
+                                                                centre, max_workspace_bytes))
+            delta = s1[0] / s0[0]
+            glob = s2[0] / s0[0] - np.outer(delta, delta) + reg_covar * np.eye(d)
+            w, cov = np.full(m, 1.0 / m), np.repeat(glob[None], m, axis=0)
+        history = []
+        for _ in range(int(n_iter)):
+            whiten, logc = cholesky_tables(w, mu, cov, "fit")
+            mu_d = rt.to_device(mu)
+            o = estep_device(rt, z, mu_d, rt.to_device(whiten), rt.to_device(logc), want=("gamma", "rowll"))
+            s0, s1, s2 = stats_device(rt, z, o["gamma"], mu_d, max_workspace_bytes)
+            history.append(float(o["rowll"].sum().item()) / n)
+            w, mu, cov = m_step(mu, s0.cpu().numpy(), s1.cpu().numpy(), s2.cpu().numpy(), reg_covar)
+    return JointGMM(w, mu, cov, dx), history
+
+
+def convert_device(rt, batch, x, gmm, mode="mlpg", windows=CONVERSION_WINDOWS):
+    """Source rows x [F][n_win d] (static then dynamic columns, as delta_features_device lays them out; the frames of
+    ``batch``) -> the target's static track [F][d_y].  'mlpg': the most likely component under the marginal of x, its
+    conditional mean rows and conditional variances, and mlpg_device over them.  'mmse': the posterior-weighted
+    conditional mean of the static columns.  'frame': the most likely component's conditional mean, static columns."""
+    from .dynamics import mlpg_device
+
+    win, _, d_y = check_convert_args(tuple(x.shape), batch.total_frames, gmm, mode, windows)
+    t = gmm.prepared(rt)
+    with rt.lock, rt.on_stream():
+        o = estep_device(rt, x, t["mu_x"], t["whiten_x"], t["logc_x"], want=("gamma",) if mode == "mmse" else ("best",))
+        if mode == "mlpg":
+            mean = convert_rows_device(rt, x, t["mu_x"], t["a"], t["mu_y"], best=o["best"])
+            var = rt.torch.index_select(t["cvar"], 0, o["best"].to(rt.torch.int64))
+            return mlpg_device(rt, batch, mean, var, windows)
+        if "a_static" not in t:  # the static columns' tables, contiguous
+            t["a_static"] = t["a"][:, :, :d_y].contiguous()
+            t["mu_y_static"] = t["mu_y"][:, :d_y].contiguous()
+        if mode == "mmse":
+            return convert_rows_device(rt, x, t["mu_x"], t["a_static"], t["mu_y_static"], g=o["gamma"])
+        return convert_rows_device(rt, x, t["mu_x"], t["a_static"], t["mu_y_static"], best=o["best"])
+
+
+# ---- mel-cepstra: CompactEncoding and the NumPy-dict forms ------------------------------------------------------------
+def _frames_batch(rt, frame_off):
+    return rt.make_batch(np.zeros(len(frame_off), dtype=np.int64), frame_off)
+
+
+def fit_mceps(rt, batch_a, mcep_a, batch_b, mcep_b, alignment, n_components, n_iter=20, windows=CONVERSION_WINDOWS, **fit_kw):
+    """fit_device on the two speakers' static + dynamic rows of mel-cepstral coefficients 1 .. n0-1, gathered through
+    ``alignment.joint``."""
+    from .dynamics import delta_features_device
+
+    check_windows(windows, "fit_conversion")
+    if mcep_a.shape[1] != mcep_b.shape[1] or int(mcep_a.shape[1]) < 2:
+        raise ValueError("fit_conversion: mel-cepstra of %d and %d coefficients" % (mcep_a.shape[1], mcep_b.shape[1]))
+    width = len(windows) * (int(mcep_a.shape[1]) - 1)
+    check_limits(2 * width, n_components, "fit_conversion")
+    with rt.lock, rt.on_stream():
+        fa = delta_features_device(rt, batch_a, mcep_a[:, 1:], windows)
+        fb = delta_features_device(rt, batch_b, mcep_b[:, 1:], windows)
+        z, _ = alignment.joint(fa, fb)
+        return fit_device(rt, z, width, n_components, n_iter, **fit_kw)
+
+
+def fit_compact(ce_a, ce_b, alignment, n_components, n_iter=20, windows=CONVERSION_WINDOWS, **fit_kw):
+    """(JointGMM, history) for two resident CompactEncodings of parallel utterances and their Alignment: the static +
+    delta rows of both speakers without coefficient 0, joined along the alignment's paths, and fit_device."""
+    for ce in (ce_a, ce_b):
+        if ce.rt is None or ce.mcep is None:
+            raise ValueError("fit_compact: the encodings must be resident (to_device(rt)) and hold a mel-cepstrum")
+    if ce_a.rt is not ce_b.rt:
+        raise ValueError("fit_compact: the two encodings live on different runtimes (device / lane)")
+    rt = ce_a.rt
+    if ce_a.total_frames != alignment.batch_a.total_frames or ce_b.total_frames != alignment.batch_b.total_frames:
+        raise ValueError("fit_compact: the alignment was not made from these encodings (%d and %d frames against %d and %d)"
+                         % (ce_a.total_frames, ce_b.total_frames, alignment.batch_a.total_frames, alignment.batch_b.total_frames))
+    with rt.lock, rt.on_stream():
+        return fit_mceps(rt, _frames_batch(rt, ce_a.frame_off), ce_a.mcep, _frames_batch(rt, ce_b.frame_off), ce_b.mcep,
+                         alignment, n_components, n_iter, windows, **fit_kw)
+
+
+def convert_mcep(rt, batch, mcep, gmm, mode="mlpg", windows=CONVERSION_WINDOWS):
+    """Mel-cepstrum [F][n0] -> the converted one: columns 1 .. n0-1 through convert_device, column 0 carried over."""
+    from .dynamics import delta_features_device
+
+    win, _ = check_windows(windows, "convert")
+    d = int(mcep.shape[1]) - 1
+    if d < 1 or len(win) * d != gmm.dx or gmm.dy != gmm.dx:
+        raise ValueError("convert: a mel-cepstrum of %d coefficients and %d windows against a model of %d + %d columns"
+                         % (d + 1, len(win), gmm.dx, gmm.dy))
+    with rt.lock, rt.on_stream():
+        x = delta_features_device(rt, batch, mcep[:, 1:], windows)
+        y = convert_device(rt, batch, x, gmm, mode, windows)
+        return rt.torch.cat([mcep[:, :1], y], dim=1)
+
+
+def convert_compact(ce, gmm, windows=CONVERSION_WINDOWS, mode="mlpg"):
+    """A new CompactEncoding whose mel-cepstral columns 1 .. n0-1 are the conversion of ``ce``'s; coefficient 0, f0, vuv,
+    band aperiodicity, the voicing gate and the frame times are carried over: ready for expand(wb) -> decode_device."""
+    if ce.rt is None:
+        raise ValueError("convert_compact: the encoding is on the host; to_device(rt) first")
+    if ce.mcep is None:
+        raise ValueError("convert_compact: the encoding keeps the dense spectrogram (compact(n0=None)): no mel-cepstrum")
+    rt = ce.rt
+    with rt.lock, rt.on_stream():
+        arrays = dict(ce._tensors())
+        arrays["mcep"] = convert_mcep(rt, _frames_batch(rt, ce.frame_off), ce.mcep, gmm, mode, windows)
+    return ce._like(rt, arrays, None if ce.tp_host is None else np.array(ce.tp_host))
+
+
+def fit_conversion_dicts(dats_a, dats_b, n_components=8, n0=40, n_iter=20, lowhz=0, highhz=8000, radius=None,
+                         windows=CONVERSION_WINDOWS, **fit_kw):
+    """World.fit_conversion: align the pairs, fit, return the JointGMM."""
+    from .align import align_encodings
+    from .batch import BatchEncoding
+
+    dats_a, dats_b = list(dats_a), list(dats_b)
+    if len(dats_a) != len(dats_b) or not dats_a:
+        raise ValueError("fit_conversion: %d dict(s) against %d: pair u is dict u of each side" % (len(dats_a), len(dats_b)))
+    check_windows(windows, "fit_conversion")
+    if int(n0) != n0 or n0 < 2:
+        raise ValueError("fit_conversion: n0 must be an integer >= 2, got %r" % (n0,))
+    check_limits(2 * len(windows) * (int(n0) - 1), n_components, "fit_conversion")
+    rt = _hip.Runtime.get()
+    with rt.lock, rt.on_stream():
+        enc_a, enc_b = BatchEncoding.from_dicts(rt, dats_a), BatchEncoding.from_dicts(rt, dats_b)
+        al = align_encodings(enc_a, enc_b, n0, lowhz, highhz, radius)
+        model, _ = fit_mceps(rt, enc_a.batch, enc_a.mcep(n0, lowhz, highhz), enc_b.batch, enc_b.mcep(n0, lowhz, highhz), al,
+                             n_components, n_iter, windows, **fit_kw)
+    return model
+
+
+def convert_voice_dict(dat, model, mode="mlpg", lowhz=0, highhz=8000, windows=CONVERSION_WINDOWS):
+    """World.convert_voice: a new dict like ``dat`` whose 'spectrogram' is decode_mcep of the converted mel-cepstrum."""
+    from .batch import BatchEncoding
+    from .compact import check_compact_args
+    from .features import imcep_device
+
+    win, _ = check_windows(windows, "convert_voice")
+    if model.dx % len(win) or model.dx != model.dy:
+        raise ValueError("convert_voice: a model of %d + %d columns does not hold %d windows per speaker"
+                         % (model.dx, model.dy, len(win)))
+    n0 = model.dx // len(win) + 1
+    fft_size = 2 * (int(np.shape(dat['spectrogram'])[0]) - 1)
+    check_compact_args(dat['fs'], fft_size, n0, "convert_voice")
+    rt = _hip.Runtime.get()
+    with rt.lock, rt.on_stream():
+        enc = BatchEncoding.from_dicts(rt, [dat])
+        mc = convert_mcep(rt, enc.batch, enc.mcep(n0, lowhz, highhz), model, mode, windows)
+        spec = rt.to_host(imcep_device(rt, mc, fft_size), transpose=True)
+    rt.check_flags("convert_voice")
+    out = {k: (np.array(v) if isinstance(v, np.ndarray) else v) for k, v in dict(dat).items() if k != 'out'}
+    out['spectrogram'] = np.ascontiguousarray(spec)
+    return out

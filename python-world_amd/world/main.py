@@ -519,6 +519,29 @@ class World(object):
             raise NotImplementedError("mlpg(devices=...): run one WorldBatch per device instead")
         return mlpg_numpy(mean, var, HTS_WINDOWS if windows is None else windows)
 
+    # ---- joint-density GMM voice conversion (not in the reference's class; world/gmm.py) ----------------------------
+    @_hip.serialised
+    def fit_conversion(self, dats_a, dats_b, n_components=8, n0=40, n_iter=20, devices=None, **kw):
+        """A conversion model from parallel utterances: encode() dicts of a source speaker and of a target speaker, pair
+        u the same sentence.  The pairs are aligned (align_batch's warping over mel-cepstra), the static + delta rows of
+        the mel-cepstral coefficients 1 .. n0-1 of both sides are joined along the paths, and a mixture of
+        ``n_components`` full-covariance Gaussians is fitted by ``n_iter`` EM iterations on the device
+        (world.gmm.fit_device; ``kw``: reg_covar, seed, init, radius, windows, ...).  Returns a world.gmm.JointGMM."""
+        from .gmm import fit_conversion_dicts
+        if devices is not None:
+            raise NotImplementedError("fit_conversion(devices=...): run one WorldBatch per device instead")
+        return fit_conversion_dicts(dats_a, dats_b, n_components, n0, n_iter, **kw)
+
+    @_hip.serialised
+    def convert_voice(self, dat, model, mode="mlpg", devices=None, **kw):
+        """An encode() dict of the source speaker -> a new dict whose spectrogram is the target speaker's under
+        ``model`` (fit_conversion's): maximum-likelihood trajectory conversion of the mel-cepstrum (``mode``: 'mlpg',
+        'mmse' or 'frame'), coefficient 0, f0, vuv and aperiodicity carried over; decode() takes it."""
+        from .gmm import convert_voice_dict
+        if devices is not None:
+            raise NotImplementedError("convert_voice(devices=...): run one WorldBatch per device instead")
+        return convert_voice_dict(dat, model, mode, **kw)
+
     # ---- modification (all in place on the dict, like the reference) ------------------------------------------
     def scale_pitch(self, dat, factor):
         """world/main.py:154-162."""
