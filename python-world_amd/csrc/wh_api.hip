@@ -124,6 +124,10 @@ int persistent_upload(wh_ctx* ctx, hipStream_t st, const std::string& slot, cons
   *dptr = e.d;
   return 0;
 }
+void* persistent_resident(wh_ctx* ctx, const std::string& slot, size_t bytes) {
+  auto it = ctx->persist.find(slot);
+  return it != ctx->persist.end() && it->second.host.size() == bytes ? it->second.d : nullptr;
+}
 int persistent_scratch(wh_ctx* ctx, const std::string& slot, size_t bytes, void** dptr) {
   wh_ctx::Persist& e = ctx->persist[slot];
   if (e.cap < bytes || !e.d) {

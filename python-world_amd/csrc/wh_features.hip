@@ -8,53 +8,40 @@
 //   encode_lfbank : pro = (a * |H(k)|)^2 / nfft (pre-emphasis, power), W = fb^T,           epi = log (0 -> eps)
 //   encode_mcep   : pro = log a,                                     W = warp + irfft rows, epi = none
 //   decode_mcep   : pro = none,                                      W = rfft rows + warp,  epi = exp
-// feature_matmul_kernel runs it on the FP64 matrix cores (v_mfma_f64_16x16x4_f64): a workgroup of four waves takes a
-// 128 x 64 output tile, each wave 32 x 64 of it; 16-wide k strips of A (prologue applied on the way in) and of W
-// (k-major, zero-padded to multiples of 32 x 16) are staged in double-buffered LDS, fetched a step ahead of the MFMAs.
+// feature_matmul_kernel runs it on the FP64 matrix cores through the staged pipeline of wh_mfma.h (operand layout, strip
+// geometry and the pipeline itself are described there): a workgroup of four waves takes a 128 x 64 output tile, each wave
+// 32 x 64 of it (8 accumulator tiles, 64 VGPRs); the 16-wide k strips are of A (prologue applied on the way in) and of W
+// (k-major, zero-padded to multiples of 32 x 16).  The first version read W from L2 in front of every MFMA and
+// single-buffered A (5.6 TFLOP/s on SWIPE's products).
 // The heads are HBM-bound (4104 B in per 32 x 8 B out for the filterbank); SWIPE's products (513-1025 x 326, 326 x ~150
 // per window size) are where the matrix cores carry weight.
-//
-// MFMA operand layout (measured, tools/ubench/mfma_check.hip): A[i][k] in lane 16k+i, B[k][j] in lane 16k+j,
-// D[4r + l/16][l%16] in register r of lane l.
 #include <math.h>
 
 #include "wh_device.h"
 #include "wh_host.h"
+#include "wh_mfma.h"
 
 namespace {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
 constexpr int kFeatKC = 32;   // W is zero-padded on the host side to multiples of 32 (k) x 16 (n)
-constexpr int kFeatKS = 16;   // k step staged in LDS per pipeline stage
 constexpr int kFeatNT = 4;    // 16-column tiles per workgroup: a 128 x 64 output tile
 constexpr int kFeatRows = 128;  // rows per workgroup: each of the four waves owns 32 x 64 = 2 x 4 MFMA tiles
-constexpr int kFeatAS = kFeatKS + 1;        // row stride of the staged A strip in doubles: 16 rows x 4 k land on distinct banks
-constexpr int kFeatBS = 16 * kFeatNT + 16;  // row stride of the staged W strip: k rows 32 banks apart
+using FeatStrip = wh::mfma_strip<kFeatNT>;
 
-// One product with prologue / epilogue, tiled for the FP64 matrix cores.  Per 16-wide k step a workgroup stages a
-// 128 x 16 strip of A (prologue applied on the way in) and the 16 x 64 strip of W in LDS — both fetched from global
-// memory into registers ONE STEP AHEAD, while the 32 MFMAs per wave of the current step run out of the other LDS buffer —
-// so the matrix pipe waits neither for HBM (A) nor for L2 (W): the first version read W from L2 in front of every MFMA and
-// single-buffered A (5.6 TFLOP/s on SWIPE's products).  Each wave keeps 8 accumulator tiles (64 VGPRs): an A operand
-// feeds four MFMAs, a W operand two.  One barrier per step.
+// One product with prologue / epilogue, tiled for the FP64 matrix cores (wh_mfma.h).
 template <int PRO, int EPI>
 __global__ __launch_bounds__(256) void feature_matmul_kernel(const double* __restrict__ A, long long n_rows, int ka,
                                                              long long lda, const double* __restrict__ P, double pscale,
                                                              const double* __restrict__ W, int kpad, int npad, int nw,
                                                              double* __restrict__ out, long long ldo) {
-  __shared__ double As[2][kFeatRows * kFeatAS];
-  __shared__ double Bs[2][kFeatKS * kFeatBS];
+  __shared__ double As[2][kFeatRows * FeatStrip::AS];
+  __shared__ double Bs[2][FeatStrip::KS * FeatStrip::BS];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const long long f0 = (long long)blockIdx.x * kFeatRows;
   const int nt0 = blockIdx.y * kFeatNT;
   const int ntiles = npad / 16;
   const int nt_here = ntiles - nt0 < kFeatNT ? ntiles - nt0 : kFeatNT;  // column tiles this workgroup really has
-  double4_t acc[2][kFeatNT];
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int t = 0; t < kFeatNT; ++t) acc[mt][t] = double4_t{0.0, 0.0, 0.0, 0.0};
+  wh::double4_t acc[2][kFeatNT] = {};
   // staging roles: thread t fetches 8 consecutive k of A row t/2 and 4 consecutive columns of W row t/16
   const int ar = threadIdx.x >> 1, ak = (threadIdx.x & 1) * 8;
   const int bk = threadIdx.x >> 4, bc = (threadIdx.x & 15) * 4;
@@ -85,34 +72,22 @@ __global__ __launch_bounds__(256) void feature_matmul_kernel(const double* __res
   };
   auto stage = [&](int buf) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) As[buf][ar * kFeatAS + ak + i] = areg[i];
+    for (int i = 0; i < 8; ++i) As[buf][ar * FeatStrip::AS + ak + i] = areg[i];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) Bs[buf][bk * kFeatBS + bc + i] = breg[i];
+    for (int i = 0; i < 4; ++i) Bs[buf][bk * FeatStrip::BS + bc + i] = breg[i];
   };
-  fetch(0);
-  stage(0);
-  __syncthreads();
-  const int steps = kpad / kFeatKS;
-  for (int st = 0; st < steps; ++st) {
-    const int buf = st & 1;
-    if (st + 1 < steps) fetch((st + 1) * kFeatKS);  // in flight under this step's MFMAs
-    const double* as = As[buf] + (32 * w + (lane & 15)) * kFeatAS + (lane >> 4);
-    const double* bs = Bs[buf] + (lane >> 4) * kFeatBS + (lane & 15);
+  wh::mfma_pipeline(kpad / FeatStrip::KS, [&](int st) { fetch(st * FeatStrip::KS); }, stage, [&](int, int buf) {
+    const double* as = As[buf] + (32 * w + (lane & 15)) * FeatStrip::AS + (lane >> 4);
+    const double* bs = Bs[buf] + (lane >> 4) * FeatStrip::BS + (lane & 15);
 #pragma unroll
-    for (int kk = 0; kk < kFeatKS / 4; ++kk) {
-      const double a0 = as[4 * kk], a1 = as[16 * kFeatAS + 4 * kk];
+    for (int kk = 0; kk < FeatStrip::KS / 4; ++kk) {
+      const double a0 = as[4 * kk], a1 = as[16 * FeatStrip::AS + 4 * kk];
 #pragma unroll
       for (int t = 0; t < kFeatNT; ++t) {
-        if (t < nt_here) {
-          const double b = bs[4 * kk * kFeatBS + 16 * t];
-          acc[0][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, acc[0][t], 0, 0, 0);
-          acc[1][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, acc[1][t], 0, 0, 0);
-        }
+        if (t < nt_here) wh::mfma_pair(acc[0][t], acc[1][t], a0, a1, bs[4 * kk * FeatStrip::BS + 16 * t]);
       }
     }
-    if (st + 1 < steps) stage(buf ^ 1);  // the other buffer was last read a step ago, before the barrier below
-    __syncthreads();
-  }
+  });
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -177,11 +152,8 @@ extern "C" int wh_feature_matmul_tagged(wh_ctx* ctx, void* stream, const double*
   double* d_p = nullptr;
   const std::string slot = table_tag ? "feat.t." + std::to_string(table_tag) + "." + shape
                                      : "feat.w." + std::to_string(prologue) + std::to_string(epilogue) + "." + shape;
-  if (table_tag) {  // a tagged table that is already resident: a pointer look-up
-    auto it = ctx->persist.find(slot);
-    if (it != ctx->persist.end() && it->second.d && it->second.host.size() == (size_t)kpad * npad * sizeof(double))
-      d_w = reinterpret_cast<double*>(it->second.d);
-  }
+  // a tagged table that is already resident: a pointer look-up
+  if (table_tag) d_w = reinterpret_cast<double*>(wh::persistent_resident(ctx, slot, (size_t)kpad * npad * sizeof(double)));
   if (!d_w) {
     std::vector<double> wp((size_t)kpad * npad, 0.0);  // zero padding: the surplus k rows / n columns contribute nothing
     for (int k = 0; k < ka; ++k)

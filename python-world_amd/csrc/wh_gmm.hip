@@ -1,16 +1,14 @@
 // Joint-density Gaussian mixtures for voice conversion (Toda, Black and Tokuda 2007): the three frame-proportional
 // computations of EM and of the conversion, each a dense FP64 product per row and component on the matrix cores
-// (v_mfma_f64_16x16x4_f64; operand layout as in wh_features.hip: A[i][k] in lane 16k+i, B[k][j] in lane 16k+j,
-// D[4r + l/16][l%16] in register r of lane l).  The per-component algebra — a d x d Cholesky factor, its inverse, the
-// regression matrices — is tiny and is done on the host (world/gmm.py).  Contract: include/world_hip.h, DESIGN section 16;
-// tests/_gmm_reference.py is the same contract in NumPy (the results agree within derived bounds, and bit for bit where
-// every partial sum is exact).
+// (wh_mfma.h: operand layout, strip geometry, pipeline).  The per-component algebra — a d x d Cholesky factor, its
+// inverse, the regression matrices — is tiny and is done on the host (world/gmm.py).  Contract: include/world_hip.h,
+// DESIGN section 16; tests/_gmm_reference.py is the same contract in NumPy (the results agree within derived bounds, and
+// bit for bit where every partial sum is exact).
 //
 // gmm_rows_kernel<MODE>: a workgroup of four waves takes 128 rows and ALL columns (up to 160: ten 16-column tiles, each
-// wave 32 rows x 160 = 2 x 10 accumulator tiles), and loops over the components m.  Per component it is
-// feature_matmul_kernel's pipeline: 16-wide k strips of (x - mu_m) (the centring applied on the way in) and of the
-// component's matrix staged in double-buffered LDS, fetched one step ahead of the MFMAs.  The matrix is read as it lies in
-// memory ([k][n] row-major); what lies beyond k or n enters as 0.0.
+// wave 32 rows x 160 = 2 x 10 accumulator tiles), and loops over the components m.  Per component it is one run of the
+// staged pipeline over 16-wide k strips of (x - mu_m) (the centring applied on the way in) and of the component's matrix,
+// read as it lies in memory ([k][n] row-major); what lies beyond k or n enters as 0.0.
 //   MODE 0 (E-step): the matrix is the upper triangular whitening W_m, so strip s needs the column tiles t >= s only (the
 //     others are structural zeros and are neither fetched nor multiplied); ll[row][m] = logc[m] - 0.5 sum_j z_j^2, the sum
 //     over a lane's tiles ascending and then over the 16 lanes of the row by a butterfly, goes to an LDS tile
@@ -24,7 +22,7 @@
 //
 // gmm_stats_kernel: s2 = sum_n gamma (x - mu)(x - mu)' is a product whose k runs over the ROWS.  With a column of ones
 // appended to the centred row, e~ = [x - mu_m, 1], the one product e~' diag(gamma) e~ holds s2, s1 (its last column) and s0
-// (its last entry).  Workgroup (m, split): the rows [split * 4096, ...) in strips of 16 staged in double-buffered LDS
+// (its last entry).  Workgroup (m, split): the rows [split * 4096, ...) in strips of 16 through the same pipeline
 // ([row][column], with gamma beside it); A = gamma * e~ (multiplied as the operand is read), B = e~.  Only the tile pairs
 // ti <= tj are computed (at most 66), dealt to the workgroup's eight waves round-robin, and of a diagonal tile only i <= j is kept: the
 // lower triangle is the MIRROR of the upper one, bit for bit.  Partials [split][m][d + 1][d + 1] go to the context's
@@ -34,22 +32,20 @@
 
 #include "wh_device.h"
 #include "wh_host.h"
+#include "wh_mfma.h"
 
 namespace {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 constexpr int kGmmMaxD = 160;  // the joint vector of 39 static + 39 delta coefficients per speaker: 156, padded
 constexpr int kGmmMaxM = 64;
 constexpr int kGmmRowTile = 128;     // rows per workgroup of gmm_rows_kernel
 constexpr int kGmmSplitRows = 4096;  // rows per partial sum of gmm_stats_kernel
 
-constexpr int kGmmKS = 16;                     // k step staged per pipeline stage
-constexpr int kGmmNT = kGmmMaxD / 16;          // column tiles of a row tile
-constexpr int kGmmAS = kGmmKS + 1;             // row stride of the staged A strip (as in wh_features.hip)
-constexpr int kGmmBS = 16 * kGmmNT + 16;       // row stride of the staged matrix strip
+constexpr int kGmmNT = kGmmMaxD / 16;             // column tiles of a row tile
 constexpr int kGmmST = (kGmmMaxD + 1 + 15) / 16;  // column tiles of the stats strip: d + 1 columns
-constexpr int kGmmES = 16 * kGmmST + 16;       // its row stride
+using GmmStrip = wh::mfma_strip<kGmmNT>;
+constexpr int kGmmKS = GmmStrip::KS, kGmmAS = GmmStrip::AS, kGmmBS = GmmStrip::BS;
+constexpr int kGmmES = wh::mfma_strip<kGmmST>::BS;  // the stats strip is a B strip: [row = k][column]
 constexpr int kGmmStatsWaves = 8;                // waves of a statistics workgroup
 constexpr int kGmmSlots = (kGmmST * (kGmmST + 1) / 2 + kGmmStatsWaves - 1) / kGmmStatsWaves;  // tile pairs per wave
 constexpr int kGmmEPer = kGmmES / 32;           // strip columns a thread stages: column t % 32 + 32 i of row t / 32
@@ -89,11 +85,11 @@ __global__ __launch_bounds__(256) void gmm_rows_kernel(
   const bool by_best = MODE == 1 && best_in_ != nullptr;
   const int32_t abest = (by_best && a_ok) ? best_in[arow] : -1;  // the staged row's component
 
-  double4_t acc[2][kGmmNT];
+  wh::double4_t acc[2][kGmmNT];
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-    for (int t = 0; t < kGmmNT; ++t) acc[mt][t] = double4_t{0.0, 0.0, 0.0, 0.0};
+    for (int t = 0; t < kGmmNT; ++t) acc[mt][t] = wh::double4_t{0.0, 0.0, 0.0, 0.0};
 
   const int passes = MODE == 0 ? M : M + 1;  // MODE 1: the last pass adds sum_m g_m mu_y[m]
   for (int m = 0; m < passes; ++m) {
@@ -104,7 +100,7 @@ __global__ __launch_bounds__(256) void gmm_rows_kernel(
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-        for (int t = 0; t < kGmmNT; ++t) acc[mt][t] = double4_t{0.0, 0.0, 0.0, 0.0};
+        for (int t = 0; t < kGmmNT; ++t) acc[mt][t] = wh::double4_t{0.0, 0.0, 0.0, 0.0};
     }
     double gm = 1.0;  // MODE 1, MMSE: the staged row's weight of this component
     if (MODE == 1 && !tail && !by_best) gm = a_ok ? g[arow * ldg + m] : 0.0;
@@ -143,6 +139,8 @@ __global__ __launch_bounds__(256) void gmm_rows_kernel(
 #pragma unroll
       for (int i = 0; i < kGmmNT; ++i) b[bk * kGmmBS + bc + 16 * i] = breg[i];
     };
+    // wh_mfma.h's pipeline, written out as it always was: this kernel's schedule (412 VGPRs) follows the text, and the
+    // forms that did not compile to the same code measured 0.7 % slower on the E-step
     fetch(0);
     stage(0);
     __syncthreads();
@@ -158,8 +156,7 @@ __global__ __launch_bounds__(256) void gmm_rows_kernel(
         for (int t = 0; t < kGmmNT; ++t) {
           if (t < ntiles && (MODE != 0 || t >= st)) {
             const double b = bs[4 * kk * kGmmBS + 16 * t];
-            acc[0][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, acc[0][t], 0, 0, 0);
-            acc[1][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, acc[1][t], 0, 0, 0);
+            wh::mfma_pair(acc[0][t], acc[1][t], a0, a1, b);
           }
         }
       }
@@ -247,7 +244,7 @@ __global__ __launch_bounds__(64 * kGmmStatsWaves) void gmm_stats_kernel(
   const int d1 = d + 1, nt = (d1 + 15) / 16, npairs = nt * (nt + 1) / 2;
   // this wave's tile pairs: pair p = kGmmStatsWaves s + w of the list (0,0) (0,1) .. (0,nt-1) (1,1) ..
   int ti[kGmmSlots], tj[kGmmSlots];
-  double4_t acc[kGmmSlots];
+  wh::double4_t acc[kGmmSlots];
 #pragma unroll
   for (int s = 0; s < kGmmSlots; ++s) {
     int a = 0, rem = kGmmStatsWaves * s + w;
@@ -260,7 +257,7 @@ __global__ __launch_bounds__(64 * kGmmStatsWaves) void gmm_stats_kernel(
       }
     ti[s] = ok ? a : -1;
     tj[s] = a + rem;
-    acc[s] = double4_t{0.0, 0.0, 0.0, 0.0};
+    acc[s] = wh::double4_t{0.0, 0.0, 0.0, 0.0};
   }
   const int rk = threadIdx.x >> 5, rc = threadIdx.x & 31;
   double ereg[kGmmEPer], greg = 0.0;
@@ -285,12 +282,7 @@ __global__ __launch_bounds__(64 * kGmmStatsWaves) void gmm_stats_kernel(
     if (rc == 0) Gs[buf][rk] = greg;
   };
   const long long steps = (r1 - r0 + kGmmKS - 1) / kGmmKS;
-  fetch(r0);
-  stage(0);
-  __syncthreads();
-  for (long long st = 0; st < steps; ++st) {
-    const int buf = (int)(st & 1);
-    if (st + 1 < steps) fetch(r0 + (st + 1) * kGmmKS);
+  wh::mfma_pipeline(steps, [&](long long st) { fetch(r0 + st * kGmmKS); }, stage, [&](long long, int buf) {
 #pragma unroll
     for (int kk = 0; kk < kGmmKS / 4; ++kk) {
       const int kr = 4 * kk + (lane >> 4);
@@ -298,16 +290,10 @@ __global__ __launch_bounds__(64 * kGmmStatsWaves) void gmm_stats_kernel(
       const double gk = Gs[buf][kr];
 #pragma unroll
       for (int s = 0; s < kGmmSlots; ++s) {
-        if (ti[s] >= 0) {
-          const double a = gk * e[16 * ti[s]];
-          const double b = e[16 * tj[s]];
-          acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[s], 0, 0, 0);
-        }
+        if (ti[s] >= 0) wh::mfma_acc(acc[s], gk * e[16 * ti[s]], e[16 * tj[s]]);
       }
     }
-    if (st + 1 < steps) stage(buf ^ 1);
-    __syncthreads();
-  }
+  });
   const long long base = (sp * M + m) * (long long)d1 * d1;
 #pragma unroll
   for (int s = 0; s < kGmmSlots; ++s) {

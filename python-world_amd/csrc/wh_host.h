@@ -97,6 +97,9 @@ int tables_make_room(wh_ctx* ctx);
 // (no device synchronisation; a context is driven from one stream at a time, so stream order protects readers of
 // the old content).  Only growing the buffer synchronises (hipFree).
 int persistent_upload(wh_ctx* ctx, hipStream_t st, const std::string& slot, const void* host, size_t bytes, void** dptr);
+// The device pointer of the persistent upload named `slot` if it holds exactly `bytes` bytes, else null: the look-up of a
+// table whose content the caller identifies by a tag, without building the host bytes to compare.
+void* persistent_resident(wh_ctx* ctx, const std::string& slot, size_t bytes);
 // A persistent device buffer of at least `bytes` under the name `slot`, contents unspecified (per-call scratch whose size
 // follows the batch shape).  Growing it synchronises the device once (earlier kernels may still use the old buffer).
 int persistent_scratch(wh_ctx* ctx, const std::string& slot, size_t bytes, void** dptr);

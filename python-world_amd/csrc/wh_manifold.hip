@@ -8,9 +8,10 @@
 // one LDS buffer (32 rows x 273 doubles, 68 KiB: the row stride is 17 mod 32 doubles so that the 16 rows x 4 k of an A
 // operand fall on distinct bank pairs); each layer reads it as its A operand, waits at a barrier, and writes its output
 // back over it.  Single buffering costs one barrier per layer and lets two workgroups share a CU's 160 KiB (eight waves,
-// two per SIMD).  Wave w computes the output column tiles 4w .. 4w+3 of every layer — 2 x 4 accumulator tiles of
-// v_mfma_f64_16x16x4f64, 64 VGPRs — with its weight k-strips loaded from L2 straight into registers one 16-k step ahead
-// of the MFMAs (each wave reads only its own columns, so the weights never pass through LDS).  Layer 0 stages its input
+// two per SIMD).  Wave w computes the output column tiles 4w .. 4w+3 of every layer — 2 x 4 accumulator tiles, 64 VGPRs
+// (wh_mfma.h: the tile type, the MFMA pair, the operand layout) — with its weight k-strips loaded from L2 straight into
+// registers one 16-k step ahead of the MFMAs (each wave reads only its own columns, so the weights never pass through
+// LDS; that is why this kernel does not run wh_mfma.h's LDS-staged pipeline).  Layer 0 stages its input
 // into the same tile, up to 256 columns at a time (the input may be up to 2048 wide), with the context gather and the
 // input shift applied on the load.  The tap layer's and the last layer's outputs leave through the tile as contiguous
 // row stores; keeping per-row global addresses in registers instead made the kernel spill.
@@ -22,9 +23,6 @@
 //
 // Every output element is one MFMA accumulation chain over k in ascending 4-steps, identical for every row of the tile:
 // a row's result does not depend on which other rows share its launch or tile.
-//
-// MFMA operand layout (tools/ubench/mfma_check.hip): A[i][k] in lane 16k+i, B[k][j] in lane 16k+j, D[4r + l/16][l%16] in
-// register r of lane l.
 #include <math.h>
 
 #include <string>
@@ -32,10 +30,9 @@
 
 #include "wh_device.h"
 #include "wh_host.h"
+#include "wh_mfma.h"
 
 namespace {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 constexpr int kDsRows = 32;      // rows per workgroup tile
 constexpr int kDsMaxW = 256;     // widest layer (units) the LDS tile holds
@@ -113,11 +110,7 @@ __global__ __launch_bounds__(256, 2) void dense_stack_kernel(
     const int t0 = kDsNT * w;
     const int nt = L.npad / 16 - t0;
     const int nt_here = nt < 0 ? 0 : (nt > kDsNT ? kDsNT : nt);
-    double4_t acc[2][kDsNT];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int t = 0; t < kDsNT; ++t) acc[mt][t] = double4_t{0.0, 0.0, 0.0, 0.0};
+    wh::double4_t acc[2][kDsNT] = {};
     // this wave's weight column li of tile t0 at k row lk: the k step and tile are uniform offsets from here
     const wh::ckp<const double> wl =
         wh::ck_sub(wt, L.w_off, (long long)L.kpad * L.npad, wh::WH_CK_TABLE) + ((long long)lk * L.npad + 16 * t0 + li);
@@ -151,10 +144,7 @@ __global__ __launch_bounds__(256, 2) void dense_stack_kernel(
           const double a0 = A[li * kDsS + k0 + 4 * kk + lk];
           const double a1 = A[(16 + li) * kDsS + k0 + 4 * kk + lk];
 #pragma unroll
-          for (int t = 0; t < kDsNT; ++t) {
-            acc[0][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, bcur[kk][t], acc[0][t], 0, 0, 0);
-            acc[1][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, bcur[kk][t], acc[1][t], 0, 0, 0);
-          }
+          for (int t = 0; t < kDsNT; ++t) wh::mfma_pair(acc[0][t], acc[1][t], a0, a1, bcur[kk][t]);
         }
       }
     };
@@ -279,15 +269,10 @@ extern "C" int wh_dense_stack(wh_ctx* ctx, void* stream, const double* x, int64_
   const std::string wslot = table_tag ? "dense.t." + std::to_string(table_tag) + "." + shape + ".w" : "dense.w";
   const std::string bslot = table_tag ? "dense.t." + std::to_string(table_tag) + "." + shape + ".b" : "dense.b";
   if (table_tag) {  // a tagged stack that is already resident: a pointer look-up
-    auto iw = ctx->persist.find(wslot);
-    auto ib = ctx->persist.find(bslot);
-    if (iw != ctx->persist.end() && iw->second.d && iw->second.host.size() == (size_t)w_total * sizeof(double) &&
-        ib != ctx->persist.end() && ib->second.d && ib->second.host.size() == (size_t)b_total * sizeof(double)) {
-      d_w = reinterpret_cast<double*>(iw->second.d);
-      d_b = reinterpret_cast<double*>(ib->second.d);
-    }
+    d_w = reinterpret_cast<double*>(wh::persistent_resident(ctx, wslot, (size_t)w_total * sizeof(double)));
+    d_b = reinterpret_cast<double*>(wh::persistent_resident(ctx, bslot, (size_t)b_total * sizeof(double)));
   }
-  if (!d_w) {
+  if (!d_w || !d_b) {
     // zero padding: surplus k rows and n columns contribute nothing, padded biases are zero
     std::vector<double> wp((size_t)w_total, 0.0), bp((size_t)b_total, 0.0);
     size_t hw = 0, hb = 0;
