@@ -81,8 +81,12 @@ int wh_bounds_last(int64_t* out4);
  * buffer — the next wh_take_flags must report WH_FLAG_OOB with the record {1, WH_CK_TABLE (7), 4, 4}. */
 int wh_bounds_selftest(wh_ctx* ctx, void* stream);
 /* Test hook: the spectral kernels' own log / exp / sincospi (csrc/wh_math.h: a few ulp, a third of the device library's
- * instructions) applied to a DEVICE array: which = 0 log -> out[n], 1 exp -> out[n], 2 (sin, cos)(pi x) -> out[2n]. */
+ * instructions) applied to a DEVICE array: which = 0 log -> out[n], 1 exp -> out[n], 2 (sin, cos)(pi x) -> out[2n];
+ * which = 3, 4, 5: the same three in their table-driven forms (tlog, texp, tsincospi), the outputs laid out alike. */
 int wh_math_probe(wh_ctx* ctx, void* stream, int which, const double* in, double* out, int64_t n);
+/* Test hook (host only, no GPU): the table of the table-driven exp and log as it is uploaded (csrc/wh_math.h: layout).
+ * h_out == NULL: returns the number of doubles; otherwise n_entries must be that number, and 0 is returned on success. */
+int wh_math_table_read(double* h_out, int64_t n_entries);
 /* Test hook: the wave-local FFT engine (wh::fft_lds_wave, csrc/wh_fft.h) on DEVICE data: `count` unnormalised complex
  * transforms of n = 512 points, interleaved (re, im) doubles, in -> out; inverse = 1: exp(+2 pi i k j / n), not divided by
  * n.  (gt, snt): threads per transform group and per workgroup, one of (64, 64), (128, 256), (256, 256). */

@@ -79,6 +79,24 @@ int const_table(wh_ctx* ctx, const std::string& key, const std::vector<double>& 
   *out = d;
   return 0;
 }
+// The table of wh_math.h's table-driven exp and log (layout there), in long double and rounded once.
+std::vector<double> math_table_host() {
+  std::vector<double> t(kMtEntries, 0.0);
+  for (int j = 0; j < 128; ++j) t[kMtExp + j] = (double)exp2l((long double)j / 128.0L);
+  for (int i = 0; i < kMtLogNodes; ++i) {
+    const double inv = (double)(float)(128.0 / (double)(kMtLogFirst + i));  // 24 bits (exactly 1 at c = 1)
+    const long double L = -logl((long double)inv);
+    const double hi = (double)(rintl(L * 0x1p42L) * 0x1p-42L);
+    t[kMtLog + 4 * i] = inv;
+    t[kMtLog + 4 * i + 1] = hi;
+    t[kMtLog + 4 * i + 2] = (double)(L - (long double)hi);
+  }
+  return t;
+}
+int math_table(wh_ctx* ctx, const double** out) {
+  if (ctx->tables.count("math_tab")) return const_table(ctx, "math_tab", std::vector<double>(), out);
+  return const_table(ctx, "math_tab", math_table_host(), out);
+}
 int tables_make_room(wh_ctx* ctx) {
   if (ctx->table_bytes <= kTableCacheBytes) return 0;
   WH_CHECK(hipDeviceSynchronize());  // kernels of earlier calls may still read them
@@ -158,7 +176,7 @@ static thread_local int64_t g_bounds_last[4] = {0, 0, 0, 0};
 
 extern "C" {
 
-int wh_version(void) { return 116; }
+int wh_version(void) { return 117; }
 const char* wh_last_error(void) { return g_last_error.c_str(); }
 
 int wh_device_count(int* count) {
@@ -266,6 +284,14 @@ static void drain_posted(wh_ctx* ctx, int32_t* h_flags16, bool accumulate) {
 }
 
 
+int wh_math_table_read(double* h_out, int64_t n_entries) {
+  if (!h_out) return wh::kMtEntries;
+  if (n_entries != wh::kMtEntries) return wh::fail_msg("wh_math_table_read", "n_entries is not the table's entry count");
+  const std::vector<double> t = wh::math_table_host();
+  memcpy(h_out, t.data(), t.size() * sizeof(double));
+  return 0;
+}
+
 int wh_bounds_build(void) {
 #if defined(WH_BOUNDS) && WH_BOUNDS
   return 1;
@@ -294,24 +320,33 @@ int wh_bounds_selftest(wh_ctx* ctx, void* stream) {
 #endif
 }
 
-// the spectral kernels' own log / exp / sincospi (wh_math.h) on a device array: which = 0 log, 1 exp, 2 sincospi (out[2i], out[2i+1])
-static __global__ void math_probe_kernel(int which, const double* __restrict__ in, double* __restrict__ out, long long n) {
+// the spectral kernels' own log / exp / sincospi (wh_math.h) on a device array: which = 0 log, 1 exp, 2 sincospi (out[2i], out[2i+1]);
+// 3, 4, 5: the same three in their table-driven forms
+static __global__ void math_probe_kernel(int which, const double* __restrict__ in, double* __restrict__ out, long long n,
+                                         const double* __restrict__ mt_raw, const double2* __restrict__ tw_raw) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  const wh::ckp<const double> mt = wh::ck_make(mt_raw, wh::kMtEntries, wh::WH_CK_TABLE);
+  const wh::ckp<const double2> tw = wh::ck_make(tw_raw, WH_TWIDDLE_ENTRIES, wh::WH_CK_TWIDDLE);
   const double x = in[i];
   if (which == 0) out[i] = wh::flog(x);
   else if (which == 1) out[i] = wh::fexp(x);
+  else if (which == 3) out[i] = wh::tlog(x, mt);
+  else if (which == 4) out[i] = wh::texp(x, mt);
   else {
-    const double2 sc = wh::fsincospi(x);
+    const double2 sc = which == 2 ? wh::fsincospi(x) : wh::tsincospi(x, tw + 256);
     out[2 * i] = sc.x;
     out[2 * i + 1] = sc.y;
   }
 }
 int wh_math_probe(wh_ctx* ctx, void* stream, int which, const double* in, double* out, int64_t n) {
-  if (!ctx || !in || !out || n < 0 || which < 0 || which > 2) return wh::fail_msg("wh_math_probe", "bad argument");
+  if (!ctx || !in || !out || n < 0 || which < 0 || which > 5) return wh::fail_msg("wh_math_probe", "bad argument");
   WH_ENTER(ctx);
   if (n == 0) return 0;
-  hipLaunchKernelGGL(math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, which, in, out, (long long)n);
+  const double* d_mt = nullptr;
+  if (int rc = wh::math_table(ctx, &d_mt)) return rc;
+  hipLaunchKernelGGL(math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, which, in, out, (long long)n,
+                     d_mt, (const double2*)ctx->d_twiddle);
   WH_LAUNCH_CHECK("math_probe_kernel");
   return 0;
 }

@@ -86,6 +86,9 @@ int ws_reserve(wh_ctx* ctx, size_t bytes);  // grows ctx->ws (hipFree + hipMallo
 inline const double2* twiddle(const wh_ctx* ctx, int n) { return ctx->d_twiddle + n; }
 // Upload-once constant table keyed by name (synchronous on first use, cached afterwards).
 int const_table(wh_ctx* ctx, const std::string& key, const std::vector<double>& host, const double** out);
+// The table of the table-driven exp / log (wh_math.h: layout, kMtEntries doubles) on the device; math_table_host: its content.
+std::vector<double> math_table_host();
+int math_table(wh_ctx* ctx, const double** out);
 // The cache is keyed by what the tables depend on — rate, window bound, F0 floor — and a long-running caller that varies
 // those (StoneMask on contours with ever new minima: a window table of up to 2 MB per distinct bound) would grow it without
 // limit.  Called at the top of the entry points that cache large tables, BEFORE any table pointer is taken: beyond

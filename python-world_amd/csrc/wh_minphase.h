@@ -23,10 +23,20 @@ __device__ __attribute__((noinline)) double4 cis_pair_call(double a0, double b0,
   sincospi(b1, &s1, &c1);
   return make_double4(e0 * c0, e0 * s0, e1 * c1, e1 * s1);
 }
+// The same through wh_math.h's table-driven forms: `tw256` is the context's twiddle table of size 256, `mt` its math table.
+// 214 -> 132 instructions per pair of bins (145 -> 95 VALU, 60 -> 25 coefficient moves); the four table values are needed
+// by the last multiplies only, the polynomials run while they are on their way.  It holds more values at once — 50 VGPRs
+// against the library form's 22 — so it is taken where the kernel has them to spare (TAB of min_phase_response).
+__device__ __attribute__((noinline)) double4 cis_pair_tab_call(double a0, double b0, double a1, double b1, wh::ckp<const double2> tw256,
+                                                               wh::ckp<const double> mt) {
+  const double2 sc0 = wh::tsincospi(b0, tw256), sc1 = wh::tsincospi(b1, tw256);
+  const double e0 = wh::texp(a0, mt), e1 = wh::texp(a1, mt);
+  return make_double4(e0 * sc0.y, e0 * sc0.x, e1 * sc1.y, e1 * sc1.x);
+}
 __device__ __attribute__((noinline)) double2 log_pair_call(double x, double y) { return make_double2(wh::flog(x), wh::flog(y)); }
 __device__ __attribute__((noinline)) double log_call(double x) { return wh::flog(x); }
-// (wh::fexp / wh::fsincospi are no shorter than the library's once the compiler has materialised their coefficients — 66 / 75
-// instructions against 56 / 82 — and read as a scalar table they stall on its latency: measured, not used)
+// (wh::tlog needs its table value — the node's reciprocal — for its FIRST instruction, so every call begins by waiting for
+// the load: measured slower than wh::flog here, not used.  wh_math.h has the numbers.)
 
 // Minimum-phase response (synthesis.py:100-116; synthesisRequiem.py:112-118) from the mirrored log-amplitude to the time
 // domain, with the O(N) passes between the three transforms fused:
@@ -39,6 +49,7 @@ __device__ __attribute__((noinline)) double log_call(double x) { return wh::flog
 //       `delay_pi` (units of pi per bin) is the pulse's fractional delay — the reference multiplies the spectrum by
 //       exp(-i*coef*shift*k) afterwards (synthesis.py:61-64); folding it into the angle saves one sincospi and one
 //       complex product per bin, and the four passes over the half spectrum become one.
+// TAB: the exponentials through cis_pair_tab_call and `mt`, the context's math table (wh_math.h); otherwise `mt` is not read.
 // `mul(k, E)`: what the minimum-phase bin k (0 <= k <= N/2) is multiplied with before the inverse transform — identity
 // for the pulse responses, the excitation frame's spectrum in the Requiem filter (synthesisRequiem.py:112-118).
 // The chain's three 512-point transforms (N = 1024, the 16 kHz shape): WAVE puts each on one wave of its GT-thread group
@@ -56,8 +67,8 @@ struct SpectrumIdentity {
 // `side(i, n)`: a job for the waves that a WAVE chain's FIRST transform leaves without butterflies (wh::fft_lds_wave) —
 // the pulse's noise run in response_pulse.  NoSide: they go straight to the transform's barrier.
 struct NoSide {};
-template <int N, int GT, bool WAVE = false, class Mul = SpectrumIdentity, class Side = NoSide>
-__device__ __forceinline__ void min_phase_response(wh::ckp<double2> zb, wh::ckp<const double2> tw_base, double delay_pi, Mul mul = Mul(),
+template <int N, int GT, bool WAVE = false, bool TAB = false, class Mul = SpectrumIdentity, class Side = NoSide>
+__device__ __forceinline__ void min_phase_response(wh::ckp<double2> zb, wh::ckp<const double2> tw_base, wh::ckp<const double> mt, double delay_pi, Mul mul = Mul(),
                                                    Side side = Side()) {
 #pragma clang fp contract(fast)
   constexpr int FT = ft_syn(N);
@@ -125,8 +136,11 @@ __device__ __forceinline__ void min_phase_response(wh::ckp<double2> zb, wh::ckp<
     // minimum-phase spectrum exp(conj(R) / N) with the fractional delay in the angle (both in units of pi)
     // the pair of bins through ONE call: the library's exp / sincospi spend a third of their instructions putting polynomial
     // coefficients into registers, and two evaluations inside one function share them
-    const double4 cis = cis_pair_call(x0.x / N, -x0.y / N * M_1_PI - delay_pi * (double)k, x1.x / N,
-                                      -x1.y / N * M_1_PI - delay_pi * (double)(M - k));
+    const double a0 = x0.x / N, b0 = -x0.y / N * M_1_PI - delay_pi * (double)k;
+    const double a1 = x1.x / N, b1 = -x1.y / N * M_1_PI - delay_pi * (double)(M - k);
+    double4 cis;
+    if constexpr (TAB) cis = cis_pair_tab_call(a0, b0, a1, b1, tw_base + 256, mt);
+    else cis = cis_pair_call(a0, b0, a1, b1);
     double2 A = mul(k, make_double2(cis.x, cis.y)), B = mul(M - k, make_double2(cis.z, cis.w));
     if (k == 0) {  // DC and Nyquist bins: only their real parts reach a real output
       A.y = 0.0;

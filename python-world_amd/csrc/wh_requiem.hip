@@ -3,9 +3,9 @@
 // band-mixed seed pulses, then frame-wise minimum-phase filtering with overlap-add.
 // ================================================================================================
 #include "wh_host.h"
-#include "wh_math.h"
 #include "wh_tid.h"  // (the opaque thread index of the spectral units)
 #include "wh_device.h"
+#include "wh_math.h"  // (behind wh_tid.h: it includes wh_device.h)
 #include "wh_fft.h"
 #include "wh_syn_types.h"
 #include "wh_minphase.h"
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(ft_syn(N), 1) void req_filter_kernel(const SynUtt* 
     wh::rfft_lds<N, FT>(sb, tw_base);
     // minimum-phase spectrum x excitation spectrum (both Hermitian, so is the product), straight into the inverse
     // transform: the fused chain of the pulse responses with the product applied to the register-held bin pairs
-    min_phase_response<N, FT>(zb, tw_base, 0.0, [&](int k, double2 e) { return wh::cmul(e, sb[k]); });
+    min_phase_response<N, FT>(zb, tw_base, wh::ckp<const double>(), 0.0, [&](int k, double2 e) { return wh::cmul(e, sb[k]); });
     // The run's sums live in LDS and go to the row ONCE, at the end of the run.  (Kept in the row itself — read, add,
     // write back per frame — the kernel is 3 % faster, 1.52 against 1.57 ms at config 4: the accumulator's 10 KB cost two
     // of its eight workgroups per CU; but every frame's 8 KB then travel to HBM and the kernel moves 2.2 GB per 64

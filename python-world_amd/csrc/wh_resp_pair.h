@@ -29,6 +29,9 @@ __device__ __forceinline__ void response_pair(const RespArgs& A, const PulseRec&
   const double2* __restrict__ tw_raw = A.tw_base;
   asm volatile("" : "+s"(tw_raw));  // per pulse: no twiddle address / value of one pulse survives into the next
   const wh::ckp<const double2> tw_base = wh::ck_make(tw_raw, WH_TWIDDLE_ENTRIES, wh::WH_CK_TWIDDLE);
+  const double* __restrict__ mt_raw = A.math_tab;
+  asm volatile("" : "+s"(mt_raw));  // (likewise)
+  const wh::ckp<const double> mt = wh::ck_make(mt_raw, wh::kMtEntries, wh::WH_CK_TABLE);
   constexpr int FT = ft_syn(N);
   constexpr int K = N / 2 + 1;
   constexpr int NZ = kRespNoise;
@@ -141,7 +144,7 @@ __device__ __forceinline__ void response_pair(const RespArgs& A, const PulseRec&
   RSTAGE_MARK(kRsNoise)
   {
     const int g = WH_TID / GT;
-    min_phase_response<N, GT, true>(g == 0 ? zbA : zbP, tw_base, 0.0, SpectrumIdentity(), noise_side);
+    min_phase_response<N, GT, true, resp_table_cis<N>()>(g == 0 ? zbA : zbP, tw_base, mt, 0.0, SpectrumIdentity(), noise_side);
   }
   RSTAGE_MARK(kRsChainsPair)
   // the means, each from its run's wave sums in wave order (response_pulse behind the chains)

@@ -62,6 +62,9 @@ __device__ __forceinline__ void response_pulse(const RespArgs& A, const PulseRec
   const double2* __restrict__ tw_raw = A.tw_base;
   asm volatile("" : "+s"(tw_raw));  // per pulse: no twiddle address / value of one pulse survives into the next
   const wh::ckp<const double2> tw_base = wh::ck_make(tw_raw, WH_TWIDDLE_ENTRIES, wh::WH_CK_TWIDDLE);
+  const double* __restrict__ mt_raw = A.math_tab;
+  asm volatile("" : "+s"(mt_raw));  // (likewise)
+  const wh::ckp<const double> mt = wh::ck_make(mt_raw, wh::kMtEntries, wh::WH_CK_TABLE);
   constexpr int FT = ft_syn(N);
   constexpr int K = N / 2 + 1;
   constexpr int NZ = kRespNoise;
@@ -273,19 +276,19 @@ __device__ __forceinline__ void response_pulse(const RespArgs& A, const PulseRec
     // (one wave per chain transforms: waves 1 and 3 of a voiced pulse, waves 1 - 3 of an unvoiced one take the noise run)
     if (NG == 2 && voiced) {
       const int g = WH_TID / GT;
-      min_phase_response<N, GT, true>(g == 0 ? zbA : zbP, tw_base, g == 0 ? 0.0 : coef_pi * shift, SpectrumIdentity(), noise_side);
+      min_phase_response<N, GT, true, resp_table_cis<N>()>(g == 0 ? zbA : zbP, tw_base, mt, g == 0 ? 0.0 : coef_pi * shift, SpectrumIdentity(), noise_side);
     } else {
-      min_phase_response<N, FT, true>(zbA, tw_base, 0.0, SpectrumIdentity(), noise_side);
-      if (voiced) min_phase_response<N, FT, true>(zbP, tw_base, coef_pi * shift);
+      min_phase_response<N, FT, true, resp_table_cis<N>()>(zbA, tw_base, mt, 0.0, SpectrumIdentity(), noise_side);
+      if (voiced) min_phase_response<N, FT, true, resp_table_cis<N>()>(zbP, tw_base, mt, coef_pi * shift);
     }
   } else if (NG == 2 && voiced) {
     const int g = WH_TID / GT;
-    min_phase_response<N, GT>(g == 0 ? zbA : zbP, tw_base, g == 0 ? 0.0 : coef_pi * shift);
+    min_phase_response<N, GT, false, resp_table_cis<N>()>(g == 0 ? zbA : zbP, tw_base, mt, g == 0 ? 0.0 : coef_pi * shift);
   } else {
     // an unvoiced pulse has no periodic response (synthesis.py:69-75): one chain, on all the threads — 40 % of the
     // pulses of speech-like input (the 500 Hz default rate of unvoiced stretches) do half the transform work
-    min_phase_response<N, FT>(zbA, tw_base, 0.0);
-    if (voiced) min_phase_response<N, FT>(zbP, tw_base, coef_pi * shift);
+    min_phase_response<N, FT, false, resp_table_cis<N>()>(zbA, tw_base, mt, 0.0);
+    if (voiced) min_phase_response<N, FT, false, resp_table_cis<N>()>(zbP, tw_base, mt, coef_pi * shift);
   }
   RSTAGE_MARK(voiced ? kRsChainsVoiced : kRsChainsUnvoiced)
   if (side_noise) {

@@ -57,6 +57,12 @@ constexpr bool resp_skip_ap() { return resp_wave_fft<N>(); }
 template <int N>
 constexpr bool resp_pairs() { return resp_wave_fft<N>() && ft_syn(N) == 256; }
 
+// The chains' complex exponentials through the table-driven forms (cis_pair_tab_call, wh_minphase.h) from N = 1024 on:
+// response_kernel 2.73 -> 2.66 ms at config 2, 35.6 -> 34.9 ms at config 5, at the registers the kernels had.  N = 512 keeps
+// the library call: the table form's live values take response_kernel<512> from 92 to 107 VGPRs and a wave per SIMD.
+template <int N>
+constexpr bool resp_table_cis() { return N >= 1024; }
+
 // Pulses per workgroup: 6 up to N = 1024, 8 beyond (measured with the pulse record prefetch in place: 4 / 5 / 6 / 7 / 8 /
 // 12 / 16 pulses 3.414 / 3.416 / 3.417 / 3.449 / 3.46 / 3.51 / 3.59 ms at config 2; at 48 kHz, N = 2048, 5 pulses 42.5
 // against 41.6 ms for 8: the flush of the longer ring is what a short run does not amortise).
@@ -99,6 +105,7 @@ struct RespArgs {
   uint64_t seed;
   const double* dc_base;
   const double2* tw_base;
+  const double* math_tab;   // wh_math.h's table (wh::math_table)
   double* rows;             // overlap-add rows of the runs (response_gather_kernel sums them into y)
   const int64_t* row_base;  // [B + 1]: where every utterance's region of `rows` begins (sized from ITS sample count)
   const int64_t* run_base;  // [n_utt + 1] first run of every utterance (pulse_run_base_kernel)

@@ -7,13 +7,13 @@
 //                     (direct convolution == the reference's truncated fftfilt), and scatter-add into
 //                     y with the reference's clipped-index semantics.
 #include "wh_host.h"
-#include "wh_math.h"
 // response_kernel walks a run of pulses in a loop and reads the thread index opaquely (wh_tid.h): with the plain index
 // every per-thread LDS / twiddle address of the ~15 transform passes in the loop body is hoisted in front of the loop and
 // kept alive across it (248 VGPRs, 2 waves per SIMD); the few integer instructions that are recomputed cost nothing
 // next to 128 spare registers.
 #include "wh_tid.h"
 #include "wh_device.h"
+#include "wh_math.h"  // (behind wh_tid.h: it includes wh_device.h)
 #include "wh_reduce.h"
 #include "wh_syn_types.h"
 #include "wh_minphase.h"
@@ -323,6 +323,8 @@ int launch_resp(wh_ctx* ctx, hipStream_t st, const RespCall& c) {
   for (int n = 0; n < N; ++n) dc[n] /= sum;
   const double* d_dc = nullptr;
   if (int rc = wh::const_table(ctx, "dc_base:" + std::to_string(N), dc, &d_dc)) return rc;
+  const double* d_mt = nullptr;
+  if (int rc = wh::math_table(ctx, &d_mt)) return rc;
   const size_t lds = sizeof(double) * RespLds<N>::kTotal;
   if (int rc = wh::allow_lds(&response_kernel<N>, lds)) return rc;
   // overlap-add rows (RunState): per utterance ceil(pcap / RUN) rows of N + 1 slots laid along the time axis.  Held in a
@@ -351,7 +353,7 @@ int launch_resp(wh_ctx* ctx, hipStream_t st, const RespCall& c) {
   WH_LAUNCH_CHECK("pulse_rows_kernel");
   // one workgroup per run of resp_run(N) pulse slots; runs past the real pulse count exit at once
   const int64_t grid = wh::xcd_grid(runs_cap * B);
-  { wh::KernelTimer _kt(ctx, st, "response_kernel"); RespArgs ra{d_meta, c.tp, c.spec, c.ap, c.fs, c.p_rec, c.p_base, B, c.noise, c.seed, d_dc, ctx->d_twiddle, reinterpret_cast<double*>(d_rows), d_row_base, reinterpret_cast<const int64_t*>(d_rb), reinterpret_cast<const int64_t*>(d_ro), runs_cap};
+  { wh::KernelTimer _kt(ctx, st, "response_kernel"); RespArgs ra{d_meta, c.tp, c.spec, c.ap, c.fs, c.p_rec, c.p_base, B, c.noise, c.seed, d_dc, ctx->d_twiddle, d_mt, reinterpret_cast<double*>(d_rows), d_row_base, reinterpret_cast<const int64_t*>(d_rb), reinterpret_cast<const int64_t*>(d_ro), runs_cap};
   hipLaunchKernelGGL(response_kernel<N>, dim3((unsigned)grid), dim3(ft_syn(N)), lds, st, ra); }
   WH_LAUNCH_CHECK("response_kernel");
   { wh::KernelTimer _kt(ctx, st, "response_gather_kernel"); hipLaunchKernelGGL(response_gather_kernel<N>, dim3((unsigned)((max_ny + kGatherTile - 1) / kGatherTile), B), dim3(256), 0, st, d_meta, p_idx, p_count, reinterpret_cast<const double*>(d_rows), d_row_base, reinterpret_cast<const int64_t*>(d_ro), runs_cap, c.y); }

@@ -11,9 +11,9 @@
 // Pulse positions are read off this arithmetic, which must round like the reference's: the unit is built with the
 // library's -ffp-contract=off and holds no contraction pragma.
 #include "wh_host.h"
-#include "wh_math.h"
 #include "wh_tid.h"  // (the opaque thread index of the spectral units)
 #include "wh_device.h"
+#include "wh_math.h"  // (behind wh_tid.h: it includes wh_device.h)
 #include "wh_reduce.h"
 #include "wh_syn_types.h"
 

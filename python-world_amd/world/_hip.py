@@ -49,6 +49,7 @@ SIGNATURES = {
     "wh_bounds_last": (_int, [_c_i64p]),
     "wh_bounds_selftest": (_int, [_vp, _vp]),
     "wh_math_probe": (_int, [_vp, _vp, _int, _vp, _vp, ctypes.c_int64]),
+    "wh_math_table_read": (_int, [_vp, ctypes.c_int64]),
     "wh_fft_probe": (_int, [_vp, _vp, _int, _int, _int, _int, _vp, _vp, ctypes.c_int64]),
     "wh_fft_engine_probe": (_int, [_vp, _vp, _int, _int, _int, _int, _int, _int, _vp, _vp, ctypes.c_int64]),
     "wh_twiddle_read": (_int, [_vp, _vp, ctypes.c_int64]),
