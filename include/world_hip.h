@@ -68,6 +68,7 @@ int wh_copy_mapped(wh_ctx* ctx, void* stream, void* dst, const void* src, size_t
 #define WH_FLAG_PULSE_OVERFLOW 4   /* more pulses than the pulse capacity, or more overlap-add rows than its row region holds */
 #define WH_FLAG_OOB 5              /* bounds build only (wh_bounds_build() == 1): a kernel indexed outside a named buffer */
 #define WH_FLAG_MLPG_PIVOT 6       /* wh_mlpg: a pivot of a system's LDL^T was not a positive finite number (non-finite or non-positive variances): that system's track is unspecified */
+#define WH_FLAG_LSF 7              /* wh_lpc_levinson: a frame's r[0] was negative or not finite, or a prediction error on the way was not a positive finite number; wh_lsf_from_lpc: the finest grid still showed fewer than p/2 sign changes of a series — that frame's outputs are NaN */
 int wh_take_flags(wh_ctx* ctx, void* stream, int32_t* h_flags16);
 /* The bounds build of the library (tools/build_variants.py ...:-DWH_BOUNDS=1; a test vehicle, never the shipped file):
  * the covered kernels index their buffers through checked pointers (csrc/wh_device.h, wh::ckp); an access outside a
@@ -542,6 +543,41 @@ int wh_gmm_convert(wh_ctx* ctx, void* stream, const double* x, int64_t n_rows, i
                    const double* mu_x, const double* a, const double* mu_y, const int32_t* best, const double* g,
                    int64_t ldg, double* out, int64_t ldo);
 int64_t wh_gmm_workspace_bytes(int64_t n_rows, int d, int M);
+
+/* ---- Line spectral frequencies: all-pole coding of the envelope at any rate (no counterpart in the reference's library) -- */
+/* Per frame and independent; tests/_lsf_reference.py is the same contract in NumPy and the results agree
+ * bit for bit.  Every sum is sequential and unfused, every product is rounded on its own and grouped as written, and no
+ * kernel evaluates a transcendental: the kernels work on x = cos w and the only trigonometry is the HOST tables below.
+ * The autocorrelation lags 0..p of a power-spectrum row are wh_feature_matmul with the table w_k cos(2 pi k m / N) / N.
+ *   wh_lpc_levinson:  r [n_frames][ldr >= p+1] -> a [n_frames][lda >= p+1] (a[0] = 1), e [n_frames] (the prediction
+ *     error), refl (may be NULL) [n_frames][ldk >= p] the reflection coefficients; 1 <= p <= 64.
+ *       E = r[0];  for n = 1..p:  acc = r[n];  for i = 1..n-1 ascending: acc += a[i] * r[n-i];  k = -(acc / E);
+ *       for i = 1..n/2: (a[i], a[n-i]) = (a[i] + k * a[n-i], a[n-i] + k * a[i]);  a[n] = k;  E = E * (1.0 - k * k).
+ *     r[0] == 0 exactly: a = e0, E = 0, refl = 0, no flag.  r[0] negative or not finite, or an E after any order that
+ *     is not positive and finite: that frame's outputs are NaN and WH_FLAG_LSF is raised; other frames are untouched.
+ *   wh_lsf_from_lpc:  a [n_frames][lda >= p+1] -> x [n_frames][ldx >= p], the cosines of the line spectral frequencies
+ *     in descending order (w ascending); p even, 2 <= p <= 64.  With m = p/2: g[0] = h[0] = a[0],
+ *     g[i] = (a[i] + a[p+1-i]) - g[i-1], h[i] = (a[i] - a[p+1-i]) + h[i-1] (P and Q without their trivial roots); the
+ *     series c[0] = g[m], c[k] = 2.0 * g[m-k] (the same with h) is evaluated by Clenshaw's recurrence
+ *       b1 = b2 = 0;  for k = m..1: (b1, b2) = ((2.0 * x) * b1 - b2) + c[k], b1;   f = (x * b1 - b2) + c[0].
+ *     h_grid[4097] (HOST) = cos(pi g / 4096).  Level G = 256, 512 .. 4096 looks at x_j = h_grid[j * 4096 / G], j = 0..G;
+ *     a bracket is a j >= 1 with (f(x_j) < 0) != (f(x_(j-1)) < 0), the first m of each series are taken, and a level at
+ *     which either series shows fewer than m gives way to the next; past 4096 the frame's row is NaN and WH_FLAG_LSF is
+ *     raised.  A bracket is bisected at most 60 times: mid = 0.5 * (lo + hi), stop when mid equals an end, the half whose
+ *     end shares the sign predicate of mid is dropped; the root is 0.5 * (lo + hi).  x[2i] is P's root i, x[2i+1] Q's.
+ *     level_out (may be NULL; int32 [n_frames], a test hook): the level that found every root, 0 for a flagged frame.
+ *   wh_lsf_envelope:  rows [n_frames][ldr >= p+1] = [E, x_1 .. x_p] -> out [n_frames][ldo >= k_bins], the power spectrum
+ *     E / |A|^2 on k_bins = N/2 + 1 bins, in product form (the polynomial is never rebuilt); h_cos[k_bins] (HOST) =
+ *     cos(pi k / (k_bins - 1)).  Per bin, c = h_cos[k]:  u = the product over i = 0, 2, .. of (2.0 * c - 2.0 * x[i]) from
+ *     1.0, v the same over i = 1, 3, ..;  A2 = 0.25 * ((2.0 * (1.0 + c)) * (u * u) + (2.0 * (1.0 - c)) * (v * v));
+ *     out = E / A2.  Rows are used as they are (world.lsf.ilsf_device repairs unsorted rows on request, in radians).
+ * All matrices DEVICE, FP64.  n_frames == 0 is no error.  Wrong arguments fail before anything is launched. */
+int wh_lpc_levinson(wh_ctx* ctx, void* stream, const double* r, int64_t n_frames, int64_t ldr, int p, double* a, int64_t lda,
+                    double* e, double* refl, int64_t ldk);
+int wh_lsf_from_lpc(wh_ctx* ctx, void* stream, const double* a, int64_t n_frames, int64_t lda, int p, const double* h_grid,
+                    int n_grid, double* x, int64_t ldx, int32_t* level_out);
+int wh_lsf_envelope(wh_ctx* ctx, void* stream, const double* rows, int64_t n_frames, int64_t ldr, int p, const double* h_cos,
+                    int k_bins, double* out, int64_t ldo);
 
 /* ---- 16-bit PCM at the batch boundary (the reference's WAV usage: example/prosody.py:12-13,57) ---------------------- */
 /* x[i] = pcm[i] / (2^15 - 1); pcm[i] = int16(trunc(y[i] * 2^15)) (low 16 bits, like NumPy's astype on the reference's

@@ -106,6 +106,12 @@ SIGNATURES = {
     "wh_gmm_convert": (_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp,
                               ctypes.c_int64, _vp, ctypes.c_int64]),
     "wh_gmm_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, _int, _int]),
+    "wh_lpc_levinson": (_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _int, _vp, ctypes.c_int64, _vp, _vp,
+                                ctypes.c_int64]),
+    "wh_lsf_from_lpc": (_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _int, ctypes.POINTER(_dbl), _int, _vp,
+                                ctypes.c_int64, _vp]),
+    "wh_lsf_envelope": (_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _int, ctypes.POINTER(_dbl), _int, _vp,
+                                ctypes.c_int64]),
     "wh_pcm16_to_f64": (_int, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
     "wh_f64_to_pcm16": (_int, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
     "wh_swipe": (_int, [_vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp]),
@@ -161,6 +167,7 @@ def same_frames(where, dense=(), **per_frame):
 # WH_FLAG_* of include/world_hip.h: sticky conditions raised by kernels instead of failing silently
 FLAG_STONEMASK_WINDOW, FLAG_EVENT_OVERFLOW, FLAG_NOISE_SHORT, FLAG_NO_PULSE, FLAG_PULSE_OVERFLOW, FLAG_OOB = range(6)
 FLAG_MLPG_PIVOT = 6
+FLAG_LSF = 7
 FLAG_MESSAGES = {
     FLAG_STONEMASK_WINDOW: "StoneMask: a frame's f0 needs a longer analysis window than the one sized from min_f0 "
                            "(frame left unrefined)",
@@ -175,6 +182,9 @@ FLAG_MESSAGES = {
     FLAG_OOB: "bounds build: a kernel indexed outside one of its buffers (world._hip.bounds_last() has the record)",
     FLAG_MLPG_PIVOT: "MLPG: a pivot of a system's factorisation was not a positive finite number (variances must be "
                      "positive and finite): that system's track is unspecified, every other system is unaffected",
+    FLAG_LSF: "LSF: a frame's autocorrelation gave no positive finite prediction error, or the finest root grid missed a "
+              "line spectral frequency (the spectrum rows must be positive and finite): that frame's rows are NaN, every "
+              "other frame is unaffected",
 }
 
 

@@ -346,7 +346,7 @@ class BatchEncoding:
         from .features import mcep_device
         return mcep_device(self.rt, self.spectrogram, n0, self.fs, lowhz, highhz)
 
-    def compact(self, n0=40, lowhz=0, highhz=8000, mcep_fs=None):
+    def compact(self, n0=40, lowhz=0, highhz=8000, mcep_fs=None, lsf_order=None):
         """The compact form of this encoding (world.compact.CompactEncoding), resident: f0 / vuv / frame times, the
         n0-coefficient mel-cepstrum of the spectrogram (encode_mcep) and D4C's band aperiodicity with its voicing gate —
         360 B per frame at 16 kHz with n0 = 40 against 8 232 dense.  Needs encode_device(want_coarse=True) (a Requiem
@@ -354,9 +354,12 @@ class BatchEncoding:
         ValueError; ``n0=None`` keeps the dense spectrogram and codes the aperiodicity only, at every rate.
         ``mcep_fs=16000``: say explicitly what the reference's feature script does implicitly — it calls
         encode_mcep(spec, n0) with the default fs = 16000 on its 22.05 kHz example (test/spectralFeatures.py:21,31-33),
-        i.e. warps the bins as if the rate were 16 kHz on both sides; the aperiodicity keeps the true rate."""
+        i.e. warps the bins as if the rate were 16 kHz on both sides; the aperiodicity keeps the true rate.
+        ``lsf_order=p`` (even, 2 .. 64): code the spectrum as line spectral frequencies instead — rows [log E, w_1 .. w_p]
+        (world.lsf.lsf_device), at EVERY sampling rate; ``n0`` and the mel-cepstrum's keywords are then not used, and
+        expand() rebuilds the all-pole envelope with world.lsf.ilsf_device."""
         from .compact import compact_encoding
-        return compact_encoding(self, n0, lowhz, highhz, mcep_fs)
+        return compact_encoding(self, n0, lowhz, highhz, mcep_fs, lsf_order)
 
     # ---- frame alignment with a parallel encoding (world/align.py) ------------------------------------------------
     def align(self, other, n0=40, lowhz=0, highhz=8000, radius=None):

@@ -12,13 +12,15 @@ device just before the synthesis, without a dense tensor crossing PCIe.
 
 The expansion of the spectrum is decode_mcep (world/main.py:343-358), which hard-codes 16 kHz and the 0-8000 Hz warp:
 `compact(n0=...)` therefore refuses other rates; `compact(n0=None)` keeps the dense spectrogram and codes the aperiodicity
-only, at every rate.  Requiem encodings already hold the band form (world/d4cRequiem.py:27-40): it is carried as it is.
+only, at every rate; `compact(lsf_order=p)` codes the spectrum as line spectral frequencies (world/lsf.py: rows
+[log E, w_1 .. w_p], expanded by ilsf_device), at every rate.  Requiem encodings already hold the band form
+(world/d4cRequiem.py:27-40): it is carried as it is.
 
 save_npz / load_npz and the argument checks are host code and need neither the library nor a GPU."""
 import numpy as np
 
 # tensors of a compact encoding in the order they travel in (all float64, frame-major)
-_FIELDS = ("temporal_positions", "f0", "vuv", "mcep", "spectrogram", "band_ap", "ap_gate")
+_FIELDS = ("temporal_positions", "f0", "vuv", "mcep", "lsf", "spectrogram", "band_ap", "ap_gate")
 
 
 def d4c_band_layout(fs, is_requiem=False):
@@ -41,17 +43,21 @@ def check_compact_args(fs, fft_size, n0, where="compact"):
 
 class CompactEncoding:
     """A batch of utterances as f0 / vuv / frame times [F], mel-cepstrum [F][n0] (or, ``n0 is None``, the dense spectrogram
-    [F][K]), band aperiodicity [F][nap] with D4C's voicing gate [F] (Requiem: the dB rows [F][nap + 2], no gate) — frames
-    of all utterances one after the other, utterance u being rows frame_off[u]:frame_off[u+1].  The tensors are torch
-    device tensors (``rt`` is the runtime they live on) or, after to_host() / load_npz(), NumPy arrays (``rt is None``)."""
+    [F][K], or line spectral frequencies ``lsf`` [F][lsf_order + 1]; ``kind`` says which), band aperiodicity [F][nap] with
+    D4C's voicing gate [F] (Requiem: the dB rows [F][nap + 2], no gate) — frames of all utterances one after the other,
+    utterance u being rows frame_off[u]:frame_off[u+1].  The tensors are torch device tensors (``rt`` is the runtime they
+    live on) or, after to_host() / load_npz(), NumPy arrays (``rt is None``)."""
 
     def __init__(self, rt, fs, fft_size, frame_period, is_requiem, n0, lowhz, highhz, frame_off, temporal_positions, f0,
-                 vuv, mcep, band_ap, ap_gate, spectrogram=None, tp_host=None, mcep_fs=None):
+                 vuv, mcep, band_ap, ap_gate, spectrogram=None, tp_host=None, mcep_fs=None, lsf=None, lsf_order=None):
         self.rt, self.fs, self.fft_size, self.frame_period = rt, fs, int(fft_size), frame_period
         self.is_requiem, self.n0, self.lowhz, self.highhz = bool(is_requiem), n0, lowhz, highhz
         self.frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
         self.temporal_positions, self.f0, self.vuv = temporal_positions, f0, vuv
         self.mcep, self.spectrogram, self.band_ap, self.ap_gate = mcep, spectrogram, band_ap, ap_gate
+        # the third spectral kind: line spectral frequencies, rows [log E, w_1 .. w_p] (world/lsf.py), at any rate
+        self.lsf = lsf
+        self.lsf_order = None if lsf is None else (int(np.shape(lsf)[1]) - 1 if lsf_order is None else int(lsf_order))
         self.tp_host = tp_host
         # the rate encode_mcep was told (its `fs` argument): the encoding's own unless compact(mcep_fs=...) said otherwise
         self.mcep_fs = None if mcep is None else (fs if mcep_fs is None else mcep_fs)
@@ -67,9 +73,15 @@ class CompactEncoding:
             shape = tuple(getattr(self, name).shape)
             if shape != (nf,):
                 raise ValueError("CompactEncoding: '%s' must hold one value per frame (%d), got shape %s" % (name, nf, shape))
-        if (self.mcep is None) == (self.spectrogram is None):
+        if self.lsf is not None:
+            from .lsf import check_order
+            if self.mcep is not None or self.spectrogram is not None:
+                raise ValueError("CompactEncoding: exactly one of mcep, lsf and spectrogram is kept")
+            check_order(self.lsf_order, "CompactEncoding", self.fft_size // 2 + 1)
+            want = ("lsf", (nf, self.lsf_order + 1))
+        elif (self.mcep is None) == (self.spectrogram is None):
             raise ValueError("CompactEncoding: exactly one of mcep and spectrogram is kept")
-        if self.mcep is not None:
+        elif self.mcep is not None:
             check_compact_args(self.mcep_fs, self.fft_size, self.n0, "CompactEncoding")
             want = ("mcep", (nf, int(self.n0)))
         else:
@@ -81,6 +93,11 @@ class CompactEncoding:
         if nap < 1 or tuple(self.band_ap.shape) != (nf, bands):
             raise ValueError("CompactEncoding: 'band_ap' must be (%d, %d) at fs = %r, got %s"
                              % (nf, bands, self.fs, tuple(self.band_ap.shape)))
+
+    @property
+    def kind(self):
+        """How the spectrum is kept: 'mcep', 'lsf' or 'spectrogram'."""
+        return "lsf" if self.lsf is not None else ("mcep" if self.mcep is not None else "spectrogram")
 
     @property
     def n_utt(self):
@@ -101,7 +118,7 @@ class CompactEncoding:
         return CompactEncoding(rt, self.fs, self.fft_size, self.frame_period, self.is_requiem, self.n0, self.lowhz,
                                self.highhz, self.frame_off, arrays["temporal_positions"], arrays["f0"], arrays["vuv"],
                                arrays.get("mcep"), arrays["band_ap"], arrays.get("ap_gate"), arrays.get("spectrogram"),
-                               tp_host=tp_host, mcep_fs=self.mcep_fs)
+                               tp_host=tp_host, mcep_fs=self.mcep_fs, lsf=arrays.get("lsf"), lsf_order=self.lsf_order)
 
     # ---- PCIe: one pinned block per direction ----------------------------------------------------------------------
     def to_host(self):
@@ -154,7 +171,11 @@ class CompactEncoding:
         ce = self.to_device(rt)
         with rt.lock, rt.on_stream():
             batch = rt.make_batch(np.zeros(ce.n_utt + 1, dtype=np.int64), ce.frame_off)
-            spec = ce.spectrogram if ce.mcep is None else imcep_device(rt, ce.mcep, ce.fft_size)
+            if ce.lsf is not None:
+                from .lsf import ilsf_device
+                spec = ilsf_device(rt, ce.lsf, ce.fft_size)
+            else:
+                spec = ce.spectrogram if ce.mcep is None else imcep_device(rt, ce.mcep, ce.fft_size)
             if ce.is_requiem:
                 ap = ce.band_ap
             else:
@@ -192,6 +213,8 @@ class CompactEncoding:
         out["lowhz"] = np.asarray(h.lowhz, dtype=np.float64)
         out["highhz"] = np.asarray(h.highhz, dtype=np.float64)
         out["mcep_fs"] = np.asarray(-1 if h.mcep_fs is None else h.mcep_fs)
+        if h.lsf is not None:  # (a file without the key is one of the other two kinds: files written before load as they did)
+            out["lsf_order"] = np.asarray(h.lsf_order)
         np.savez(path, **out)
 
     @classmethod
@@ -205,7 +228,8 @@ class CompactEncoding:
                    bool(g["is_requiem"]), None if n0 < 0 else n0, g["lowhz"].item(), g["highhz"].item(), g["frame_off"],
                    g["temporal_positions"], g["f0"], g["vuv"], g.get("mcep"), g["band_ap"], g.get("ap_gate"),
                    g.get("spectrogram"), tp_host=g["temporal_positions"],
-                   mcep_fs=None if g["mcep_fs"].item() == -1 else g["mcep_fs"].item())
+                   mcep_fs=None if g["mcep_fs"].item() == -1 else g["mcep_fs"].item(), lsf=g.get("lsf"),
+                   lsf_order=int(g["lsf_order"]) if "lsf_order" in g else None)
 
     # ---- plain dicts (World.encode_compact_batch / decode_compact_batch) ---------------------------------------------
     def to_dicts(self):
@@ -222,10 +246,38 @@ class CompactEncoding:
                  "fs": h.fs, "fft_size": h.fft_size, "is_requiem": h.is_requiem}
             if h.mcep is not None:
                 d["mcep"] = h.mcep[s].copy()
+            elif h.lsf is not None:
+                d["lsf"] = h.lsf[s].copy()
             else:
                 d["spectrogram"] = np.ascontiguousarray(h.spectrogram[s].T)
             out.append(d)
         return out
+
+    @classmethod
+    def _from_lsf_dicts(cls, dats):
+        d0 = dats[0]
+        fs, fft_size, req = d0["fs"], int(d0["fft_size"]), bool(d0["is_requiem"])
+        p = int(np.shape(d0["lsf"])[1]) - 1 if np.ndim(d0["lsf"]) == 2 else None
+        _, nap = d4c_band_layout(fs, req)
+        bands = nap + 2 if req else nap
+        for n, d in enumerate(dats):
+            if d["fs"] != fs or int(d["fft_size"]) != fft_size or bool(d["is_requiem"]) != req:
+                raise ValueError("dict %d: the dicts of one batch must share fs, fft_size and is_requiem" % n)
+            nf = len(d["f0"])
+            per_frame = [("temporal_positions", (nf,)), ("f0", (nf,)), ("vuv", (nf,)), ("coarse_ap", (bands, nf)),
+                         ("lsf", (nf, None if p is None else p + 1))]
+            if not req:
+                per_frame.append(("ap_gate", (nf,)))
+            for key, shape in per_frame:
+                if key not in d or d[key] is None or np.shape(d[key]) != shape:
+                    raise ValueError("dict %d: '%s' must have shape %s, got %s"
+                                     % (n, key, shape, None if d.get(key) is None else np.shape(d[key])))
+        cat = lambda key, t=False: np.concatenate(  # noqa: E731
+            [np.asarray(d[key], dtype=np.float64).T if t else np.asarray(d[key], dtype=np.float64) for d in dats])
+        tp = cat("temporal_positions")
+        frame_off = np.concatenate([[0], np.cumsum([len(d["f0"]) for d in dats])])
+        return cls(None, fs, fft_size, None, req, None, 0, 8000, frame_off, tp, cat("f0"), cat("vuv"), None, cat("coarse_ap", True), None if req else cat("ap_gate"), None,
+                   tp_host=tp, lsf=cat("lsf"), lsf_order=p)
 
     @classmethod
     def from_dicts(cls, dats):
@@ -235,6 +287,8 @@ class CompactEncoding:
             raise ValueError("CompactEncoding.from_dicts: no dicts")
         d0 = dats[0]
         fs, fft_size, req = d0["fs"], int(d0["fft_size"]), bool(d0["is_requiem"])
+        if "lsf" in d0:
+            return cls._from_lsf_dicts(dats)
         coded = "mcep" in d0
         n0 = int(np.shape(d0["mcep"])[1]) if coded and np.ndim(d0["mcep"]) == 2 else None
         check_compact_args(fs, fft_size, n0 if coded else None, "CompactEncoding.from_dicts")
@@ -262,8 +316,32 @@ class CompactEncoding:
                    None if coded else cat("spectrogram", True), tp_host=tp)
 
 
-def compact_encoding(enc, n0=40, lowhz=0, highhz=8000, mcep_fs=None):
+def _bands_of(enc):
+    if enc.is_requiem:
+        return enc.aperiodicity, None
+    band_ap, gate = getattr(enc, "coarse_ap", None), getattr(enc, "ap_gate", None)
+    if band_ap is None or gate is None:
+        raise ValueError("compact: this encoding holds no band aperiodicity: encode with want_coarse=True")
+    return band_ap, gate
+
+
+def _compact_lsf(enc, lsf_order):
+    """compact(lsf_order=p): the spectrum as line spectral frequencies, at any sampling rate."""
+    from .lsf import check_order, lsf_device
+    p = check_order(lsf_order, "compact", enc.fft_size // 2 + 1)
+    band_ap, gate = _bands_of(enc)
+    rt = enc.rt
+    with rt.lock, rt.on_stream():
+        rows = lsf_device(rt, enc.spectrogram, p)
+    return CompactEncoding(rt, enc.fs, enc.fft_size, enc.frame_period, enc.is_requiem, None, 0, 8000, enc.batch.frame_off,
+                           enc.temporal_positions, enc.f0, enc.vuv, None, band_ap, gate, None, tp_host=enc.tp_host,
+                           lsf=rows, lsf_order=p)
+
+
+def compact_encoding(enc, n0=40, lowhz=0, highhz=8000, mcep_fs=None, lsf_order=None):
     """BatchEncoding.compact: see there."""
+    if lsf_order is not None:
+        return _compact_lsf(enc, lsf_order)
     mcep_fs = enc.fs if mcep_fs is None else mcep_fs
     check_compact_args(mcep_fs, enc.fft_size, n0, "compact")
     rt = enc.rt

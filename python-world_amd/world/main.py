@@ -635,6 +635,26 @@ class World(object):
     def get_context(self, X, w=5):
         return _feat.get_context(X, w)
 
+    # ---- line spectral frequencies (world/lsf.py; no counterpart in the reference's library) -----------------------
+    def encode_lsf(self, spec, order=24):
+        """(N, D) power spectrogram (encode()'s 'spectrogram', transposed) -> (N, order + 1) rows [log E, w_1 .. w_p]:
+        the log of the all-pole gain and the line spectral frequencies in radians, ascending.  ``order`` even, 2 .. 64;
+        valid at every sampling rate."""
+        from . import lsf as _lsf
+        return _lsf.encode_lsf(spec, order)
+
+    def decode_lsf(self, lsf, fft_size, min_gap=0.0):
+        """(N, p + 1) rows of encode_lsf -> the (N, fft_size / 2 + 1) all-pole power spectrogram.  ``min_gap`` > 0
+        (radians) first repairs rows that are out of order or closer than that (world/lsf.py)."""
+        from . import lsf as _lsf
+        return _lsf.decode_lsf(lsf, fft_size, min_gap)
+
+    def encode_lpc(self, spec, order=24):
+        """(N, D) power spectrogram -> (a (N, order + 1) with a[:, 0] = 1, the prediction-error gain E (N,), the
+        reflection coefficients (N, order))."""
+        from . import lsf as _lsf
+        return _lsf.encode_lpc(spec, order)
+
     # ---- manifold vocoder (world/main.py:367-384; world/manifold.py) ----------------------------------------------
     def encode_vae(self, Xc, energy, encoder, decoder, window, n0, batch_size, mean):
         """MCEP -> latent -> MCEP through the VAE's encoder and decoder (world/main.py:367-384), both networks in one
