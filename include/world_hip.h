@@ -293,6 +293,20 @@ int wh_synthesis_render(wh_ctx* ctx, void* stream, const wh_batch* b, const wh_c
 int wh_synthesis_plan(wh_ctx* ctx, void* stream, const wh_batch* b, const double* tp, const double* f0,
                       const double* vuv, double fs, const int64_t* h_y_off, const double* h_t0, const double* h_dt,
                       int64_t pulse_cap, int32_t* h_pulse_count, int64_t* h_noise_total);
+/* Test hook (read-only, no kernel): what the last wh_synthesis_timebase of ctx (also the one inside wh_synthesis) left
+ * in its workspace, copied to HOST arrays so that every pulse can be compared with the reference's field by field.
+ * Fails with "no time base" unless ctx holds one (any call that lays the workspace out again drops it), and when
+ * n_utt, pulse_cap or n_samples are not that time base's.  Waits for `stream`.  Any output may be NULL.
+ *   h_count[n_utt]: pulses per utterance (clipped to pulse_cap); h_base[n_utt + 1]: their exclusive prefix (p_base).
+ *   Per pulse, n_utt * pulse_cap entries each of which the first h_base[n_utt] are written, utterance by utterance in
+ *   time order: h_pidx (1-based sample index), h_time (pulse_locations), h_shift, h_noff (offset into the utterance's
+ *   noise stream), h_noise_size (next index - this one, 0 for the last), h_vuv, h_row_lo / h_row_hi (the two frames the
+ *   pulse interpolates between, relative to the utterance's first frame), h_weight (of the later frame; -1: one frame).
+ *   Per output sample, n_samples entries: h_phase (cumulative phase), h_vuv_s (interpolated vuv > 0.5). */
+int wh_synthesis_timebase_read(wh_ctx* ctx, void* stream, int n_utt, int64_t pulse_cap, int64_t n_samples,
+                               int32_t* h_count, int64_t* h_base, int64_t* h_pidx, double* h_time, double* h_shift,
+                               int64_t* h_noff, int32_t* h_noise_size, int32_t* h_vuv, int64_t* h_row_lo,
+                               int64_t* h_row_hi, double* h_weight, double* h_phase, uint8_t* h_vuv_s);
 
 /* The device noise of wh_synthesis / wh_synthesis_render (noise == NULL), exposed for sample-exact checks: out[i]
  * (DEVICE, n doubles) = sample q0 + i of the standard-normal stream that utterance `utt` of a batch reads under

@@ -48,6 +48,8 @@ struct wh_ctx {
     int n_utt = 0;
     int64_t pulse_cap = 0, ny_tot = 0, frames = 0;
     size_t o_vuv = 0, o_pt = 0, o_pi = 0, o_ps = 0, o_pn = 0, o_pc = 0, o_pb = 0, o_rec = 0;
+    size_t o_phase = 0;
+    std::vector<int64_t> f_off;  // first frame of every utterance (wh_synthesis_timebase_read makes the rows relative)
   } timebase;
   // Harvest's zero-crossing lists (wh_harvest_set_event_caps / wh_harvest_event_counts): the capacities the NEXT
   // wh_harvest takes instead of its estimate (one-shot; empty: estimate, hv_caps_worst: ylen/2 + 2 for every list), and

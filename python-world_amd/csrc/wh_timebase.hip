@@ -756,6 +756,63 @@ extern "C" int wh_synthesis_timebase(wh_ctx* ctx, void* stream, const wh_batch* 
   t.frames = b->total_frames;
   t.o_vuv = lay.o_vuv; t.o_pt = lay.o_pt; t.o_pi = lay.o_pi; t.o_ps = lay.o_ps; t.o_pn = lay.o_pn; t.o_pc = lay.o_pc; t.o_pb = o_pb;
   t.o_rec = o_rec;
+  t.o_phase = lay.o_phase;
+  t.f_off.assign(b->h_frame_off.begin(), b->h_frame_off.begin() + B);
+  return 0;
+}
+
+// What that call left, on the host (see world_hip.h): copies only — no launch, nothing in the workspace changes.
+extern "C" int wh_synthesis_timebase_read(wh_ctx* ctx, void* stream, int n_utt, int64_t pulse_cap, int64_t n_samples,
+                                          int32_t* h_count, int64_t* h_base, int64_t* h_pidx, double* h_time,
+                                          double* h_shift, int64_t* h_noff, int32_t* h_noise_size, int32_t* h_vuv,
+                                          int64_t* h_row_lo, int64_t* h_row_hi, double* h_weight, double* h_phase,
+                                          uint8_t* h_vuv_s) {
+  if (!ctx) return wh::fail_msg("wh_synthesis_timebase_read", "null ctx");
+  const wh_ctx::TimeBase& t = ctx->timebase;
+  if (!t.valid) return wh::fail_msg("wh_synthesis_timebase_read", "no time base (run wh_synthesis_timebase on this context, and nothing that uses its workspace since)");
+  if (t.n_utt != n_utt || t.pulse_cap != pulse_cap || t.ny_tot != n_samples)
+    return wh::fail_msg("wh_synthesis_timebase_read", "n_utt, pulse_cap or n_samples are not the time base's");
+  WH_ENTER(ctx);
+  WH_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  const char* ws = reinterpret_cast<const char*>(ctx->ws);
+  const int B = t.n_utt;
+  std::vector<int32_t> count((size_t)B);
+  std::vector<int64_t> base((size_t)B + 1);
+  WH_CHECK(hipMemcpy(count.data(), ws + t.o_pc, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+  WH_CHECK(hipMemcpy(base.data(), ws + t.o_pb, sizeof(int64_t) * (B + 1), hipMemcpyDeviceToHost));
+  for (int u = 0; u < B; ++u) {
+    if (count[u] < 0 || count[u] > pulse_cap || base[0] != 0 || base[u + 1] - base[u] != count[u])
+      return wh::fail_msg("wh_synthesis_timebase_read", "the pulse counts in the workspace are not a time base's");
+    if (h_count) h_count[u] = count[u];
+    if (h_base) h_base[u] = base[u];
+  }
+  if (h_base) h_base[B] = base[B];
+  const int64_t total = base[B];
+  if (total < 0 || total > (int64_t)B * pulse_cap)
+    return wh::fail_msg("wh_synthesis_timebase_read", "the pulse counts in the workspace are not a time base's");
+  std::vector<PulseRec> rec((size_t)total);
+  if (total > 0) WH_CHECK(hipMemcpy(rec.data(), ws + t.o_rec, sizeof(PulseRec) * (size_t)total, hipMemcpyDeviceToHost));
+  for (int64_t g = 0; g < total; ++g) {
+    const PulseRec& r = rec[(size_t)g];
+    const int64_t f0 = (r.u >= 0 && r.u < B) ? t.f_off[(size_t)r.u] : 0;
+    if (h_pidx) h_pidx[g] = r.pidx;
+    if (h_shift) h_shift[g] = r.shift;
+    if (h_noff) h_noff[g] = r.noff;
+    if (h_noise_size) h_noise_size[g] = r.noise_size;
+    if (h_vuv) h_vuv[g] = r.vuv;
+    if (h_row_lo) h_row_lo[g] = (r.rows & 0xffffffffll) - f0;
+    if (h_row_hi) h_row_hi[g] = ((r.rows >> 32) & 0xffffffffll) - f0;
+    if (h_weight) h_weight[g] = r.weight;
+  }
+  if (h_time) {  // p_time lies in pulse slots: pulse i of utterance u at u * pulse_cap + i
+    for (int u = 0; u < B; ++u) {
+      if (count[u] > 0)
+        WH_CHECK(hipMemcpy(h_time + base[u], ws + t.o_pt + sizeof(double) * (size_t)u * (size_t)pulse_cap,
+                           sizeof(double) * (size_t)count[u], hipMemcpyDeviceToHost));
+    }
+  }
+  if (h_phase && n_samples > 0) WH_CHECK(hipMemcpy(h_phase, ws + t.o_phase, sizeof(double) * (size_t)n_samples, hipMemcpyDeviceToHost));
+  if (h_vuv_s && n_samples > 0) WH_CHECK(hipMemcpy(h_vuv_s, ws + t.o_vuv, (size_t)n_samples, hipMemcpyDeviceToHost));
   return 0;
 }
 

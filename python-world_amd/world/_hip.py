@@ -68,6 +68,7 @@ SIGNATURES = {
     "wh_synthesis": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _int, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp,
                             ctypes.c_uint64, _vp, _vp]),
     "wh_synthesis_timebase": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, ctypes.c_int64, _dbl]),
+    "wh_synthesis_timebase_read": (_int, [_vp, _vp, _int, ctypes.c_int64, ctypes.c_int64] + [_vp] * 13),
     "wh_synthesis_render": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _int, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp,
                                    ctypes.c_uint64, _vp, _vp]),
     "wh_philox_normals": (_int, [_vp, _vp, ctypes.c_uint64, _int, ctypes.c_int64, ctypes.c_int64, _vp]),

@@ -48,6 +48,37 @@ def synthesis_timebase_device(rt_tb, batch, tp_d, f0_d, vuv_d, fs, ny_list, t0_l
                                                float(f0_low_limit)))
 
 
+def synthesis_timebase_read(rt_tb, n_utt, pulse_cap, ny_list):
+    """What the last ``synthesis_timebase_device`` (or wh_synthesis) of ``rt_tb``'s context left in its workspace, read
+    back to the host (wh_synthesis_timebase_read: a test hook, copies only).  Returns one dict per utterance: ``count``,
+    per pulse ``pidx``, ``time``, ``shift``, ``noff``, ``noise_size``, ``vuv``, ``row_lo``, ``row_hi`` (frames relative to
+    the utterance's first), ``weight``; per sample ``phase`` (cumulative) and ``vuv_s``; and ``base``, the utterance's first
+    pulse in the batch's flat numbering.  Raises WorldHipError when the context holds no such time base."""
+    n_utt, pulse_cap = int(n_utt), int(pulse_cap)
+    y_off = np.concatenate([[0], np.cumsum(ny_list)]).astype(np.int64)
+    slots = n_utt * pulse_cap
+    count = np.zeros(n_utt, dtype=np.int32)
+    base = np.zeros(n_utt + 1, dtype=np.int64)
+    per_pulse = {"pidx": np.int64, "time": np.float64, "shift": np.float64, "noff": np.int64, "noise_size": np.int32,
+                 "vuv": np.int32, "row_lo": np.int64, "row_hi": np.int64, "weight": np.float64}
+    out = {k: np.zeros(slots, dtype=t) for k, t in per_pulse.items()}
+    phase = np.zeros(int(y_off[-1]), dtype=np.float64)
+    vuv_s = np.zeros(int(y_off[-1]), dtype=np.uint8)
+    vp = ctypes.c_void_p
+    _hip.check(rt_tb.lib.wh_synthesis_timebase_read(
+        rt_tb.ctx, rt_tb.stream(), n_utt, pulse_cap, int(y_off[-1]), count.ctypes.data_as(vp), base.ctypes.data_as(vp),
+        *[out[k].ctypes.data_as(vp) for k in ("pidx", "time", "shift", "noff", "noise_size", "vuv", "row_lo", "row_hi",
+                                               "weight")],
+        phase.ctypes.data_as(vp), vuv_s.ctypes.data_as(vp)))
+    res = []
+    for u in range(n_utt):
+        d = {k: v[base[u]:base[u + 1]].copy() for k, v in out.items()}
+        d.update(count=int(count[u]), base=int(base[u]), phase=phase[y_off[u]:y_off[u + 1]].copy(),
+                 vuv_s=vuv_s[y_off[u]:y_off[u + 1]].copy())
+        res.append(d)
+    return res
+
+
 def synthesis_device(rt, batch, tp_d, f0_d, vuv_d, spec_d, ap_d, fs, fft_size, ny_list, t0_list, dt_list,
                      noise_d=None, noise_off=None, seed=0, pulse_cap=None, timebase_rt=None):
     """Device-resident core.  spec_d/ap_d are frame-major [F][K].  Returns the concatenated waveform tensor.

@@ -86,6 +86,27 @@ def _cases():
     yield y, 128
 
 
+def _switch_cases():
+    """tests/test_hip_cumsum.py's patterns and tile-edge lengths at a small tile: the model, NumPy and the device agree on
+    the same data shapes (the device's tile is 4096, its switch to these passes at more than 64 tiles)"""
+    from _timebase_cases import scan_patterns
+
+    for tile, n in ((128, 64 * 128 + 777), (256, 20000)):
+        for _, x in scan_patterns(n, zeros=tile + tile // 4):
+            yield x, tile
+    rng = np.random.RandomState(99)
+    tile = 64
+    for n in (tile - 1, tile, tile + 1, 2 * tile - 1, 2 * tile, 2 * tile + 1, 64 * tile - 1, 64 * tile, 64 * tile + 1, 65 * tile):
+        yield rng.uniform(0.01, 0.1, n), tile
+        yield 2 * np.pi * (90 + 60 * np.sin(np.arange(n) / 80.0)) / 16000.0, tile
+
+
+def test_tile_scan_model_on_the_device_tests_patterns():
+    for x, tile in _switch_cases():
+        got, _ = tile_scan_model(x, tile)
+        assert np.array_equal(got.view(np.int64), np.cumsum(x).view(np.int64)), (len(x), tile)
+
+
 def test_tile_scan_model_equals_cumsum_bitwise():
     for x, tile in _cases():
         got, _ = tile_scan_model(x, tile)
