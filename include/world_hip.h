@@ -593,6 +593,34 @@ int wh_lsf_from_lpc(wh_ctx* ctx, void* stream, const double* a, int64_t n_frames
 int wh_lsf_envelope(wh_ctx* ctx, void* stream, const double* rows, int64_t n_frames, int64_t ldr, int p, const double* h_cos,
                     int k_bins, double* out, int64_t ldo);
 
+/* ---- A chain over line spectral frequencies: repair and scoring (no counterpart in the reference's library) ------------- */
+/* Per frame / per pair and independent; tests/_lsf_chain_reference.py is the same contract in NumPy.
+ *   wh_lsf_repair:  w [n_frames][ldw >= p] angles in radians -> out [n_frames][ldo >= p], decodable: inside [gap, hi]
+ *     and at least gap apart; 2 <= p <= 64, gap > 0, hi >= gap (world.lsf passes min_gap and the double pi - min_gap).
+ *     out == w (in place) is allowed; otherwise the two must not overlap.  In this order, max / min giving NaN when
+ *     either operand is one (torch.maximum / minimum, not fmax / fmin), every + and - rounded once:
+ *       1. w[i] = min(max(w[i], gap), hi) for every i;     2. w[i] = max(w[i], w[i-1] + gap), i = 1 .. p-1 ascending;
+ *       3. w[p-1] = min(w[p-1], hi);                        4. w[i] = min(w[i], w[i+1] - gap), i = p-2 .. 0 descending.
+ *     The result equals world.lsf.repair_rows bit for bit.  changed (may be NULL; int32 [n_frames]): the number of
+ *     angles of the frame whose output bits differ from the input bits.  No flag is raised; a frame's result depends on
+ *     its own row only (a NaN spreads inside its row as the four steps carry it).
+ *   wh_lsf_distortion:  rows_a [n_rows_a][lda >= p+1], rows_b [n_rows_b][ldb >= p+1] in wh_lsf_envelope's form
+ *     [., x_1 .. x_p] (cosines, descending; column 0 is not read); p even, 2 <= p <= 64.  Pair n compares row idx_a[n] of
+ *     a with row idx_b[n] of b (DEVICE int64 [n_pairs]; either may be NULL: row n).  h_cos[k_bins] (HOST) as for
+ *     wh_lsf_envelope.  Per bin, c = h_cos[k]: u, v and A2 of each side exactly as wh_lsf_envelope forms them;
+ *     q = A2_a / A2_b (one division); t = log q, the device library's logarithm (<= 1 ulp).
+ *       out[n][0] = sum over the k_bins bins of t;   out[n][1] = sum of t * t.
+ *     The order of the two sums is not part of the contract; it is fixed (no atomics), so the same pair gives the same
+ *     bits on every run, alone or among other pairs.  Two identical rows give (0.0, 0.0) exactly.  An index outside
+ *     [0, n_rows) reads nothing and gives that pair (NaN, NaN); a non-finite row, or a root that coincides with a bin's
+ *     cosine, flows through as inf / NaN in that pair only.  out: DEVICE [n_pairs][2].
+ * All matrices DEVICE, FP64.  n_frames == 0 / n_pairs == 0 is no error.  Wrong arguments fail before anything is launched. */
+int wh_lsf_repair(wh_ctx* ctx, void* stream, const double* w, int64_t n_frames, int64_t ldw, int p, double gap, double hi,
+                  double* out, int64_t ldo, int32_t* changed);
+int wh_lsf_distortion(wh_ctx* ctx, void* stream, const double* rows_a, int64_t n_rows_a, int64_t lda, const double* rows_b,
+                      int64_t n_rows_b, int64_t ldb, int p, const int64_t* idx_a, const int64_t* idx_b, int64_t n_pairs,
+                      const double* h_cos, int k_bins, double* out);
+
 /* ---- 16-bit PCM at the batch boundary (the reference's WAV usage: example/prosody.py:12-13,57) ---------------------- */
 /* x[i] = pcm[i] / (2^15 - 1); pcm[i] = int16(trunc(y[i] * 2^15)) (low 16 bits, like NumPy's astype on the reference's
  * platform).  DEVICE pointers: the 2-byte samples cross PCIe instead of the 8-byte ones. */

@@ -113,6 +113,9 @@ SIGNATURES = {
                                 ctypes.c_int64, _vp]),
     "wh_lsf_envelope": (_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _int, ctypes.POINTER(_dbl), _int, _vp,
                                 ctypes.c_int64]),
+    "wh_lsf_repair": (_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _int, _dbl, _dbl, _vp, ctypes.c_int64, _vp]),
+    "wh_lsf_distortion": (_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64, _int,
+                                 _vp, _vp, ctypes.c_int64, ctypes.POINTER(_dbl), _int, _vp]),
     "wh_pcm16_to_f64": (_int, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
     "wh_f64_to_pcm16": (_int, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
     "wh_swipe": (_int, [_vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp]),

@@ -133,6 +133,25 @@ class Alignment:
         coefficients 1 .. n0-1."""
         return self.mean_cost() * MCD_SCALE
 
+    def lsd_db(self, rows_a, rows_b, fft_size, gain=False):
+        """The aligned log-spectral distortion in dB per pair, device tensor [n_utt]: the mean over the pair's path of
+        world.lsf.distortion_device between row path_a of ``rows_a`` and row path_b of ``rows_b`` — rows
+        [log E, w_1 .. w_p] of line spectral frequencies over the frames of the two batches (the aligned ones, or any
+        others on the same frames: a conversion scored against its target).  ``gain=False``: the distortion of the
+        spectral shape, the best constant gain taken out of every cell.  What mcd_db() is to mel-cepstral rows."""
+        from .lsf import distortion_device
+
+        rt, torch = self.rt, self.rt.torch
+        for name, rows, batch in (("rows_a", rows_a, self.batch_a), ("rows_b", rows_b, self.batch_b)):
+            if rows.dim() != 2 or int(rows.shape[0]) != batch.total_frames:
+                raise ValueError("lsd_db: %s must be [%d frames][p + 1], got %s" % (name, batch.total_frames, tuple(rows.shape)))
+        with rt.lock, rt.on_stream():
+            pos, off = self.valid_index()
+            d = distortion_device(rt, rows_a, rows_b, fft_size, self.path_a.index_select(0, pos),
+                                  self.path_b.index_select(0, pos), gain)
+            lengths = torch.from_numpy(np.diff(off)).to(rt.device)
+            return torch.segment_reduce(d, "mean", lengths=lengths)
+
     def pairs(self, u):
         """(i, j): pair u's path as two host arrays of utterance-local frame indices."""
         o, n = int(self.path_off_host[u]), int(self.lengths()[u])
@@ -246,6 +265,44 @@ def align_encodings(enc_a, enc_b, n0=40, lowhz=0, highhz=8000, radius=None,
     with rt.lock, rt.on_stream():
         ma, mb = enc_a.mcep(n0, lowhz, highhz), enc_b.mcep(n0, lowhz, highhz)
         return align_device(rt, enc_a.batch, ma[:, 1:], enc_b.batch, mb[:, 1:], radius,
+                            max_workspace_bytes=max_workspace_bytes)
+
+
+def check_compact_pair(ce_a, ce_b, where="align_compact"):
+    """ValueError unless the two CompactEncodings can be compared row by row: the same kind ('mcep' or 'lsf'), the same
+    number of coefficients and the same sampling rate.  Touches no device.  Returns the number of columns compared."""
+    if ce_a.kind != ce_b.kind or ce_a.kind == "spectrogram":
+        raise ValueError("%s: encodings of kind %r and %r: both must hold a mel-cepstrum, or both line spectral frequencies"
+                         % (where, ce_a.kind, ce_b.kind))
+    if ce_a.fs != ce_b.fs:
+        raise ValueError("%s: sampling rates differ (%r, %r): the rows would not be comparable" % (where, ce_a.fs, ce_b.fs))
+    if ce_a.kind == "lsf":
+        if ce_a.lsf_order != ce_b.lsf_order:
+            raise ValueError("%s: line spectral frequencies of order %d and %d" % (where, ce_a.lsf_order, ce_b.lsf_order))
+        return ce_a.lsf_order
+    if ce_a.n0 != ce_b.n0 or ce_a.mcep_fs != ce_b.mcep_fs:
+        raise ValueError("%s: mel-cepstra of %r coefficients at %r Hz and of %r at %r Hz"
+                         % (where, ce_a.n0, ce_a.mcep_fs, ce_b.n0, ce_b.mcep_fs))
+    return int(ce_a.n0) - 1
+
+
+def align_compact(ce_a, ce_b, radius=None, max_workspace_bytes=DEFAULT_MAX_WORKSPACE_BYTES):
+    """CompactEncoding.align: dynamic time warping of utterance u of ``ce_a`` against utterance u of ``ce_b`` over the
+    stored rows — mcep[:, 1:], or the p angles lsf[:, 1:]; coefficient 0 / the gain is dropped — so a corpus kept as
+    compact .npz files is aligned without its spectrograms.  Both encodings resident on one runtime.  Returns an Alignment."""
+    d = check_compact_pair(ce_a, ce_b)
+    if ce_a.rt is None or ce_b.rt is None:
+        raise ValueError("align_compact: the encodings must be resident (to_device(rt))")
+    if ce_a.rt is not ce_b.rt:
+        raise ValueError("align_compact: the two encodings live on different runtimes (device / lane)")
+    check_radius(radius)
+    check_pair_shapes(ce_a.frame_off, ce_b.frame_off, d, "align_compact")
+    rt = ce_a.rt
+    key = ce_a.kind
+    with rt.lock, rt.on_stream():
+        zeros = np.zeros(ce_a.n_utt + 1, dtype=np.int64)
+        return align_device(rt, rt.make_batch(zeros, ce_a.frame_off), getattr(ce_a, key)[:, 1:],
+                            rt.make_batch(zeros, ce_b.frame_off), getattr(ce_b, key)[:, 1:], radius,
                             max_workspace_bytes=max_workspace_bytes)
 
 

@@ -185,19 +185,28 @@ class CompactEncoding:
 
     # ---- dynamic features and parameter generation (world/dynamics.py) ---------------------------------------------------
     def dynamic_features(self, windows=None):
-        """What a statistical model of this encoding is trained on: {"mcep": [F][n_win n0], "band_ap": [F][n_win bands]},
+        """What a statistical model of this encoding is trained on: {"mcep": [F][n_win n0], "band_ap": [F][n_win bands]}
+        ({"lsf": [F][n_win (p + 1)], "band_ap": ...} for line spectral frequencies),
         column w * d + c being window w (static, delta, delta-delta for the default HTS_WINDOWS) over column c; no window
         reaches across an utterance.  Device tensors; the encoding must be resident."""
         from .dynamics import HTS_WINDOWS, compact_dynamic_features
         return compact_dynamic_features(self, HTS_WINDOWS if windows is None else windows)
 
-    def with_trajectories(self, mcep=None, band_ap=None, windows=None):
+    def with_trajectories(self, mcep=None, band_ap=None, windows=None, lsf=None, min_gap=None):
         """A new CompactEncoding whose 'mcep' / 'band_ap' are the maximum-likelihood tracks (world.dynamics.mlpg_device) of
         the given (mean, var) pairs — mean [F][n_win d] laid out like dynamic_features(), var the same shape or one row
         [n_win d]; None keeps this encoding's tensor.  f0, vuv, the voicing gate and the frame times are carried over:
-        the result is ready for expand(wb) -> decode_device."""
+        the result is ready for expand(wb) -> decode_device.  An encoding of line spectral frequencies takes ``lsf``
+        instead of ``mcep`` (the other one is a ValueError): the p + 1 columns are generated, then the angles are
+        repaired with ``min_gap`` > 0 radians (world.lsf.repair_device) — a generated track is not ordered."""
         from .dynamics import HTS_WINDOWS, compact_with_trajectories
-        return compact_with_trajectories(self, mcep, band_ap, HTS_WINDOWS if windows is None else windows)
+        return compact_with_trajectories(self, mcep, band_ap, HTS_WINDOWS if windows is None else windows, lsf, min_gap)
+
+    def align(self, other, radius=None):
+        """world.align.align_compact(self, other, radius): dynamic time warping against another resident CompactEncoding of
+        the same sentences, over the mel-cepstral coefficients 1 .. n0-1 or the p angles — no spectrogram is needed."""
+        from .align import align_compact
+        return align_compact(self, other, radius)
 
     # ---- files (host only) -------------------------------------------------------------------------------------------
     def save_npz(self, path):

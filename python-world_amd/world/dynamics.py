@@ -169,25 +169,36 @@ def compact_dynamic_features(ce, windows=HTS_WINDOWS):
     check_windows(windows, "dynamic_features")
     if ce.rt is None:
         raise ValueError("dynamic_features: the encoding is on the host; to_device(rt) first")
-    if ce.mcep is None:
+    if ce.mcep is None and ce.lsf is None:
         raise ValueError("dynamic_features: the encoding keeps the dense spectrogram (compact(n0=None)): no mel-cepstrum")
     rt = ce.rt
+    key = "mcep" if ce.lsf is None else "lsf"  # (LSF rows: the p + 1 columns [log E, w_1 .. w_p])
     with rt.lock, rt.on_stream():
         batch = rt.make_batch(np.zeros(ce.n_utt + 1, dtype=np.int64), ce.frame_off)
-        return {"mcep": delta_features_device(rt, batch, ce.mcep, windows),
+        return {key: delta_features_device(rt, batch, getattr(ce, key), windows),
                 "band_ap": delta_features_device(rt, batch, ce.band_ap, windows)}
 
 
-def compact_with_trajectories(ce, mcep=None, band_ap=None, windows=HTS_WINDOWS):
+def compact_with_trajectories(ce, mcep=None, band_ap=None, windows=HTS_WINDOWS, lsf=None, min_gap=None):
     """CompactEncoding.with_trajectories: see there."""
     win, _ = check_windows(windows, "with_trajectories")
+    if mcep is not None and ce.lsf is not None:
+        raise ValueError("with_trajectories: mcep= on an encoding that holds line spectral frequencies: pass lsf=")
+    if lsf is not None and ce.lsf is None:
+        raise ValueError("with_trajectories: lsf= on an encoding that holds no line spectral frequencies (kind %r)" % ce.kind)
     if ce.rt is None:
         raise ValueError("with_trajectories: the encoding is on the host; to_device(rt) first")
     if mcep is not None and ce.mcep is None:
         raise ValueError("with_trajectories: the encoding keeps the dense spectrogram (compact(n0=None)): no mel-cepstrum")
+    if lsf is not None:
+        from .lsf import check_min_gap, repair_device
+        if min_gap is None or not check_min_gap(min_gap, ce.lsf_order, "with_trajectories") > 0:
+            raise ValueError("with_trajectories: lsf= needs min_gap > 0 (radians): a generated track decodes only after "
+                             "the repair")
     rt = ce.rt
     nf = ce.total_frames
     for name, pair, width in (("mcep", mcep, None if ce.mcep is None else int(ce.mcep.shape[1])),
+                              ("lsf", lsf, None if ce.lsf is None else int(ce.lsf.shape[1])),
                               ("band_ap", band_ap, int(ce.band_ap.shape[1]))):
         if pair is None:
             continue
@@ -200,6 +211,10 @@ def compact_with_trajectories(ce, mcep=None, band_ap=None, windows=HTS_WINDOWS):
         arrays = dict(ce._tensors())
         if mcep is not None:
             arrays["mcep"] = mlpg_device(rt, batch, mcep[0], mcep[1], windows)
+        if lsf is not None:  # the gain and the angles are generated alike; the angles are then made decodable, in place
+            rows = mlpg_device(rt, batch, lsf[0], lsf[1], windows)
+            repair_device(rt, rows[:, 1:], min_gap, out=rows[:, 1:])
+            arrays["lsf"] = rows
         if band_ap is not None:
             arrays["band_ap"] = mlpg_device(rt, batch, band_ap[0], band_ap[1], windows)
     return ce._like(rt, arrays, None if ce.tp_host is None else np.array(ce.tp_host))

@@ -87,9 +87,21 @@ def m_step(means, s0, s1, s2, reg_covar):
 
 class JointGMM:
     """A mixture over joint rows [x; y]: weights [M], means [M][D], covariances [M][D][D] (host float64), the first
-    ``dx`` columns being the source's."""
+    ``dx`` columns being the source's.  ``kind`` says what the rows are made of: 'mcep' (mel-cepstral coefficients
+    1 .. n0-1) or 'lsf' (the ``lsf_order`` angles of line spectral frequencies); for 'lsf', ``lsf_min_gap`` is the
+    smallest of w_1, pi - w_p and any adjacent gap over the target's training rows — the default repair of a conversion,
+    which is then never sharper than anything the target speaker produced.  A model does not know the sampling rate of
+    the rows it was fitted on: angles of the same order from another rate are converted without complaint (they mean other
+    frequencies), so keep a model with the corpus it came from."""
 
-    def __init__(self, weights, means, covariances, dx):
+    def __init__(self, weights, means, covariances, dx, kind="mcep", lsf_order=None, lsf_min_gap=None):
+        if kind not in ("mcep", "lsf"):
+            raise ValueError("JointGMM: kind must be 'mcep' or 'lsf', got %r" % (kind,))
+        if (kind == "lsf") != (lsf_order is not None) or (kind == "lsf") != (lsf_min_gap is not None):
+            raise ValueError("JointGMM: lsf_order and lsf_min_gap belong to kind 'lsf' and to no other")
+        self.kind = kind
+        self.lsf_order = None if lsf_order is None else int(lsf_order)
+        self.lsf_min_gap = None if lsf_min_gap is None else float(lsf_min_gap)
         self.weights = np.ascontiguousarray(weights, dtype=np.float64)
         self.means = np.ascontiguousarray(means, dtype=np.float64)
         self.covariances = np.ascontiguousarray(covariances, dtype=np.float64)
@@ -145,12 +157,18 @@ class JointGMM:
         return self._dev[key]
 
     def save_npz(self, path):
-        np.savez(path, weights=self.weights, means=self.means, covariances=self.covariances, dx=np.asarray(self.dx))
+        out = {"weights": self.weights, "means": self.means, "covariances": self.covariances, "dx": np.asarray(self.dx)}
+        if self.kind == "lsf":  # (a file without the keys is a mel-cepstral model: files written before load as they did)
+            out.update(kind=np.asarray("lsf"), lsf_order=np.asarray(self.lsf_order), lsf_min_gap=np.asarray(self.lsf_min_gap))
+        np.savez(path, **out)
 
     @classmethod
     def load_npz(cls, path):
         with np.load(path) as z:
-            return cls(z["weights"], z["means"], z["covariances"], int(z["dx"]))
+            if "kind" not in z.files:
+                return cls(z["weights"], z["means"], z["covariances"], int(z["dx"]))
+            return cls(z["weights"], z["means"], z["covariances"], int(z["dx"]), str(z["kind"]), int(z["lsf_order"]),
+                       float(z["lsf_min_gap"]))
 
 
 def check_convert_args(x_shape, frames, gmm, mode, windows, where="convert"):
@@ -346,17 +364,75 @@ def fit_compact(ce_a, ce_b, alignment, n_components, n_iter=20, windows=CONVERSI
     """(JointGMM, history) for two resident CompactEncodings of parallel utterances and their Alignment: the static +
     delta rows of both speakers without coefficient 0, joined along the alignment's paths, and fit_device."""
     for ce in (ce_a, ce_b):
-        if ce.rt is None or ce.mcep is None:
-            raise ValueError("fit_compact: the encodings must be resident (to_device(rt)) and hold a mel-cepstrum")
+        if ce.rt is None or (ce.mcep is None and ce.lsf is None):
+            raise ValueError("fit_compact: the encodings must be resident (to_device(rt)) and hold a mel-cepstrum or line "
+                             "spectral frequencies")
+    if ce_a.kind != ce_b.kind or ce_a.lsf_order != ce_b.lsf_order:
+        raise ValueError("fit_compact: the two encodings differ in kind or order (%r %r against %r %r)"
+                         % (ce_a.kind, ce_a.lsf_order, ce_b.kind, ce_b.lsf_order))
+    if ce_a.lsf is not None and ce_a.fs != ce_b.fs:
+        raise ValueError("fit_compact: sampling rates differ (%r, %r): the angles would not be comparable" % (ce_a.fs, ce_b.fs))
     if ce_a.rt is not ce_b.rt:
         raise ValueError("fit_compact: the two encodings live on different runtimes (device / lane)")
     rt = ce_a.rt
     if ce_a.total_frames != alignment.batch_a.total_frames or ce_b.total_frames != alignment.batch_b.total_frames:
         raise ValueError("fit_compact: the alignment was not made from these encodings (%d and %d frames against %d and %d)"
                          % (ce_a.total_frames, ce_b.total_frames, alignment.batch_a.total_frames, alignment.batch_b.total_frames))
+    if ce_a.lsf is not None:
+        check_lsf_width(ce_a.lsf_order, windows, "fit_compact")
     with rt.lock, rt.on_stream():
+        if ce_a.lsf is not None:
+            return fit_lsf(rt, _frames_batch(rt, ce_a.frame_off), ce_a.lsf, _frames_batch(rt, ce_b.frame_off), ce_b.lsf,
+                           alignment, n_components, n_iter, windows, **fit_kw)
         return fit_mceps(rt, _frames_batch(rt, ce_a.frame_off), ce_a.mcep, _frames_batch(rt, ce_b.frame_off), ce_b.mcep,
                          alignment, n_components, n_iter, windows, **fit_kw)
+
+
+# ---- line spectral frequencies: the same chain over the p angles, at any sampling rate ----------------------------------
+def check_lsf_width(p, windows, where="fit_conversion"):
+    """ValueError for an order whose joint rows the kernels do not take: n_win p columns per speaker, 2 n_win p <= 160
+    (p <= 40 with CONVERSION_WINDOWS)."""
+    n_win = len(windows)
+    if 2 * n_win * int(p) > MAX_D:
+        raise ValueError("%s: line spectral frequencies of order %d with %d windows give joint rows of %d columns; the "
+                         "kernels take at most %d columns (order <= %d)" % (where, p, n_win, 2 * n_win * int(p), MAX_D,
+                                                                           MAX_D // (2 * n_win)))
+
+
+def lsf_min_gap(rows):
+    """The smallest of w_1, pi - w_p and any adjacent gap over rows [F][p + 1] = [log E, w_1 .. w_p] (a torch tensor or
+    a NumPy array): how sharp the sharpest envelope of these rows is, as a host float.  Each term is one rounded
+    subtraction; a NaN anywhere gives NaN."""
+    w = rows[:, 1:]
+    parts = [float(w[:, 0].min()), float((float(np.pi) - w[:, -1]).min()), float((w[:, 1:] - w[:, :-1]).min())]
+    return float("nan") if any(v != v for v in parts) else min(parts)
+
+
+def fit_lsf(rt, batch_a, lsf_a, batch_b, lsf_b, alignment, n_components, n_iter=20, windows=CONVERSION_WINDOWS, **fit_kw):
+    """fit_mceps over rows [log E, w_1 .. w_p]: the gain is dropped as coefficient 0 is, the model is marked 'lsf' and
+    keeps the target's smallest gap."""
+    p = int(lsf_a.shape[1]) - 1
+    check_lsf_width(p, windows)
+    gap = lsf_min_gap(lsf_b)
+    if not (gap > 0.0 and np.isfinite(gap)):
+        raise ValueError("fit_conversion: the target's line spectral frequencies are not strictly ascending inside "
+                         "(0, pi) (smallest gap %r)" % gap)
+    model, history = fit_mceps(rt, batch_a, lsf_a, batch_b, lsf_b, alignment, n_components, n_iter, windows, **fit_kw)
+    return JointGMM(model.weights, model.means, model.covariances, model.dx, "lsf", p, gap), history
+
+
+def convert_lsf(rt, batch, lsf, gmm, mode="mlpg", windows=CONVERSION_WINDOWS, min_gap=None):
+    """Rows [F][p + 1] -> the converted rows: the angles through convert_device, then repaired (``min_gap``: the model's
+    lsf_min_gap when None); log E carried over."""
+    from .lsf import repair_device
+
+    if gmm.kind != "lsf" or gmm.lsf_order != int(lsf.shape[1]) - 1:
+        raise ValueError("convert: rows of line spectral frequencies of order %d against a model of kind %r, order %r"
+                         % (int(lsf.shape[1]) - 1, gmm.kind, gmm.lsf_order))
+    with rt.lock, rt.on_stream():
+        rows = convert_mcep(rt, batch, lsf, gmm, mode, windows)
+        repair_device(rt, rows[:, 1:], gmm.lsf_min_gap if min_gap is None else min_gap, out=rows[:, 1:])
+    return rows
 
 
 def convert_mcep(rt, batch, mcep, gmm, mode="mlpg", windows=CONVERSION_WINDOWS):
@@ -374,23 +450,53 @@ def convert_mcep(rt, batch, mcep, gmm, mode="mlpg", windows=CONVERSION_WINDOWS):
         return rt.torch.cat([mcep[:, :1], y], dim=1)
 
 
-def convert_compact(ce, gmm, windows=CONVERSION_WINDOWS, mode="mlpg"):
+def convert_compact(ce, gmm, windows=CONVERSION_WINDOWS, mode="mlpg", min_gap=None):
     """A new CompactEncoding whose mel-cepstral columns 1 .. n0-1 are the conversion of ``ce``'s; coefficient 0, f0, vuv,
-    band aperiodicity, the voicing gate and the frame times are carried over: ready for expand(wb) -> decode_device."""
+    band aperiodicity, the voicing gate and the frame times are carried over: ready for expand(wb) -> decode_device.
+    An encoding of line spectral frequencies (and a model fitted on such) converts the p angles, log E carried over, and
+    ends with the repair (``min_gap``: the model's lsf_min_gap when None)."""
     if ce.rt is None:
         raise ValueError("convert_compact: the encoding is on the host; to_device(rt) first")
-    if ce.mcep is None:
+    if ce.mcep is None and ce.lsf is None:
         raise ValueError("convert_compact: the encoding keeps the dense spectrogram (compact(n0=None)): no mel-cepstrum")
+    if ce.kind != gmm.kind or ce.lsf_order != gmm.lsf_order:
+        raise ValueError("convert_compact: an encoding of kind %r, order %r against a model of kind %r, order %r"
+                         % (ce.kind, ce.lsf_order, gmm.kind, gmm.lsf_order))
     rt = ce.rt
     with rt.lock, rt.on_stream():
         arrays = dict(ce._tensors())
+        if ce.lsf is not None:
+            arrays["lsf"] = convert_lsf(rt, _frames_batch(rt, ce.frame_off), ce.lsf, gmm, mode, windows, min_gap)
+            return ce._like(rt, arrays, None if ce.tp_host is None else np.array(ce.tp_host))
         arrays["mcep"] = convert_mcep(rt, _frames_batch(rt, ce.frame_off), ce.mcep, gmm, mode, windows)
     return ce._like(rt, arrays, None if ce.tp_host is None else np.array(ce.tp_host))
 
 
+def _fit_conversion_lsf(dats_a, dats_b, n_components, lsf_order, n_iter, radius, windows, fit_kw):
+    from .align import align_device
+    from .batch import BatchEncoding
+    from .lsf import check_order, lsf_device
+
+    rates = {d['fs'] for d in dats_a} | {d['fs'] for d in dats_b}
+    if len(rates) != 1:
+        raise ValueError("fit_conversion: sampling rates differ (%s): the rows would not be comparable" % sorted(rates))
+    p = check_order(lsf_order, "fit_conversion")
+    check_lsf_width(p, windows)
+    check_limits(2 * len(windows) * p, n_components, "fit_conversion")
+    rt = _hip.Runtime.get()
+    with rt.lock, rt.on_stream():
+        enc_a, enc_b = BatchEncoding.from_dicts(rt, dats_a), BatchEncoding.from_dicts(rt, dats_b)
+        la, lb = lsf_device(rt, enc_a.spectrogram, p), lsf_device(rt, enc_b.spectrogram, p)
+        al = align_device(rt, enc_a.batch, la[:, 1:], enc_b.batch, lb[:, 1:], radius)
+        model, _ = fit_lsf(rt, enc_a.batch, la, enc_b.batch, lb, al, n_components, n_iter, windows, **fit_kw)
+    rt.check_flags("fit_conversion")
+    return model
+
+
 def fit_conversion_dicts(dats_a, dats_b, n_components=8, n0=40, n_iter=20, lowhz=0, highhz=8000, radius=None,
-                         windows=CONVERSION_WINDOWS, **fit_kw):
-    """World.fit_conversion: align the pairs, fit, return the JointGMM."""
+                         windows=CONVERSION_WINDOWS, lsf_order=None, **fit_kw):
+    """World.fit_conversion: align the pairs, fit, return the JointGMM.  ``lsf_order``: over line spectral frequencies of
+    that order instead of the mel-cepstrum, at any sampling rate."""
     from .align import align_encodings
     from .batch import BatchEncoding
 
@@ -398,6 +504,8 @@ def fit_conversion_dicts(dats_a, dats_b, n_components=8, n0=40, n_iter=20, lowhz
     if len(dats_a) != len(dats_b) or not dats_a:
         raise ValueError("fit_conversion: %d dict(s) against %d: pair u is dict u of each side" % (len(dats_a), len(dats_b)))
     check_windows(windows, "fit_conversion")
+    if lsf_order is not None:
+        return _fit_conversion_lsf(dats_a, dats_b, n_components, lsf_order, n_iter, radius, windows, fit_kw)
     if int(n0) != n0 or n0 < 2:
         raise ValueError("fit_conversion: n0 must be an integer >= 2, got %r" % (n0,))
     check_limits(2 * len(windows) * (int(n0) - 1), n_components, "fit_conversion")
@@ -422,6 +530,17 @@ def convert_voice_dict(dat, model, mode="mlpg", lowhz=0, highhz=8000, windows=CO
                          % (model.dx, model.dy, len(win)))
     n0 = model.dx // len(win) + 1
     fft_size = 2 * (int(np.shape(dat['spectrogram'])[0]) - 1)
+    if model.kind == "lsf":  # at any sampling rate: the spectrogram is ilsf of the converted rows
+        from .lsf import ilsf_device, lsf_device
+        rt = _hip.Runtime.get()
+        with rt.lock, rt.on_stream():
+            enc = BatchEncoding.from_dicts(rt, [dat])
+            rows = convert_lsf(rt, enc.batch, lsf_device(rt, enc.spectrogram, model.lsf_order), model, mode, windows)
+            spec = rt.to_host(ilsf_device(rt, rows, fft_size), transpose=True)
+        rt.check_flags("convert_voice")
+        out = {k: (np.array(v) if isinstance(v, np.ndarray) else v) for k, v in dict(dat).items() if k != 'out'}
+        out['spectrogram'] = np.ascontiguousarray(spec)
+        return out
     check_compact_args(dat['fs'], fft_size, n0, "convert_voice")
     rt = _hip.Runtime.get()
     with rt.lock, rt.on_stream():

@@ -14,13 +14,15 @@ tests/_lsf_reference.py states in NumPy and the device reproduces bit for bit; t
 trigonometry is the three host tables below plus torch.acos / torch.cos / log / exp on the small [F][p] result here.
 
 Rows that a model produced (interpolated, converted, generated) may be out of order or too close: ``min_gap`` (radians)
-repairs them before the envelope — here, in radians, with torch's elementwise max / min / + / -: clamp into [gap, pi - gap],
-a forward pass w[i] = max(w[i], w[i-1] + gap), the last angle back under pi - gap, and a backward pass
-w[i] = min(w[i], w[i+1] - gap).
+repairs them before the envelope, in radians: clamp into [gap, pi - gap], a forward pass w[i] = max(w[i], w[i-1] + gap),
+the last angle back under pi - gap, and a backward pass w[i] = min(w[i], w[i+1] - gap).  repair_rows states it with
+torch's elementwise max / min / + / - (about 2 p + 2 launches, each over one strided column); repair_device is the same
+arithmetic in one kernel, wh_lsf_repair (csrc/wh_lsf_chain.hip), one read and one write of the tensor, the same bits.
 
-The generic delta_features_device / mlpg_device / world.gmm.fit_device accept any [frames][d] tensor and so accept LSF rows
-as they are; CompactEncoding.dynamic_features / with_trajectories, BatchEncoding.align and world.gmm's compact helpers
-are wired to the mel-cepstrum only.
+The voice-conversion chain runs over these rows at every rate: CompactEncoding.dynamic_features /
+with_trajectories / align, world.align.align_compact and world.gmm's fit_compact / convert_compact take the kind 'lsf',
+and a conversion is scored by the log-spectral distortion of two rows' envelopes on aligned frames — distortion_device,
+Alignment.lsd_db — which wh_lsf_distortion forms from the two rows in product form, without either envelope in memory.
 
 The tables and the argument checks are host code and need neither the library nor a GPU."""
 import ctypes
@@ -174,18 +176,126 @@ def repair_rows(torch, w, min_gap):
     return w
 
 
+def check_min_gap(min_gap, p, where="repair"):
+    """ValueError unless 0 <= min_gap < pi / (p + 2): p angles at least that far apart and from 0 and pi must fit."""
+    if not 0 <= float(min_gap) < np.pi / (int(p) + 2):
+        raise ValueError("%s: min_gap must be in [0, pi / (p + 2)), got %r" % (where, min_gap))
+    return float(min_gap)
+
+
+def repair_device(rt, w, min_gap, want_changed=False, out=None):
+    """wh_lsf_repair: the angles [F][p] (a column slice of the rows is fine) made decodable, in one pass — repair_rows'
+    arithmetic step for step, the same bits.  ``min_gap`` > 0.  ``out``: where to (w itself: in place); a new tensor when
+    None.  ``want_changed``: (angles, changed int32 [F]) — how many angles of each frame the repair moved."""
+    _check_rows(rt, "w", w, "repair", 2)
+    f, p = int(w.shape[0]), int(w.shape[1])
+    if p > MAX_ORDER:
+        raise ValueError("repair: rows of %d angles; the kernel takes 2 .. %d" % (p, MAX_ORDER))
+    gap = check_min_gap(min_gap, p)
+    if not gap > 0:
+        raise ValueError("repair: min_gap must be positive, got %r" % (min_gap,))
+    with rt.lock, rt.on_stream():
+        if out is None:
+            out = rt.empty((f, p))
+        else:
+            _check_rows(rt, "out", out, "repair", 2)
+            if tuple(out.shape) != (f, p):
+                raise ValueError("repair: out must be %s, got %s" % ((f, p), tuple(out.shape)))
+        changed = rt.empty((f,), dtype=rt.torch.int32) if want_changed else None
+        _hip.check(rt.lib.wh_lsf_repair(rt.ctx, rt.stream(), rt.ptr(w), f, _ld(w), p, gap, float(np.pi - gap), rt.ptr(out),
+                                        _ld(out), rt.ptr(changed)))
+    return (out, changed) if want_changed else out
+
+
 def ilsf_device(rt, rows_d, fft_size, min_gap=0.0):
     """Rows [F][p + 1] = [log E, w_1 .. w_p] -> the power spectrum [F][fft_size // 2 + 1].  ``min_gap`` = 0: the rows are
-    used as they are; > 0: repaired first (module docstring)."""
+    used as they are; > 0: repaired first (module docstring; wh_lsf_repair)."""
     k_bins = check_fft_size(fft_size)
     _check_rows(rt, "rows", rows_d, "ilsf", 3)
-    check_order(int(rows_d.shape[1]) - 1, "ilsf")
-    if not 0 <= float(min_gap) < np.pi / (int(rows_d.shape[1]) + 1):
-        raise ValueError("ilsf: min_gap must be in [0, pi / (p + 2)), got %r" % (min_gap,))
+    p = check_order(int(rows_d.shape[1]) - 1, "ilsf")
+    gap = check_min_gap(min_gap, p, "ilsf")
     torch = rt.torch
     with rt.lock, rt.on_stream():
-        ex = torch.cat([torch.exp(rows_d[:, :1]), torch.cos(repair_rows(torch, rows_d[:, 1:], float(min_gap)))], dim=1)
+        w = repair_device(rt, rows_d[:, 1:], gap) if gap > 0 else rows_d[:, 1:]
+        ex = torch.cat([torch.exp(rows_d[:, :1]), torch.cos(w)], dim=1)
         return envelope_device(rt, ex, k_bins)
+
+
+LSD_SCALE = 10.0 / np.log(10.0)
+
+
+def _index(rt, idx, n_pairs, name):
+    if idx is None:
+        return None
+    if idx.dim() != 1 or idx.dtype != rt.torch.int64 or not idx.is_contiguous() or int(idx.shape[0]) != n_pairs:
+        raise ValueError("lsf_distortion: %s must be a contiguous int64 tensor [%d], got %s %s"
+                         % (name, n_pairs, idx.dtype, tuple(idx.shape)))
+    return idx
+
+
+def distortion_sums_device(rt, ex_a, ex_b, k_bins, idx_a=None, idx_b=None):
+    """wh_lsf_distortion on rows [., x_1 .. x_p] (COSINES, as envelope_device takes them): [n_pairs][2] = (sum over the
+    bins of t, sum of t * t), t = log(A2_a / A2_b).  Pair n is row idx_a[n] against row idx_b[n] (int64 device tensors,
+    batch-global frame indices as Alignment.path_a / path_b hold them), or row n where an index is None."""
+    _check_rows(rt, "rows_a", ex_a, "lsf_distortion", 3)
+    _check_rows(rt, "rows_b", ex_b, "lsf_distortion", 3)
+    p = check_order(int(ex_a.shape[1]) - 1, "lsf_distortion")
+    if int(ex_b.shape[1]) != p + 1:
+        raise ValueError("lsf_distortion: rows of order %d against rows of order %d" % (p, int(ex_b.shape[1]) - 1))
+    if idx_a is None and idx_b is None and int(ex_a.shape[0]) != int(ex_b.shape[0]):
+        raise ValueError("lsf_distortion: %d rows against %d and no indices" % (int(ex_a.shape[0]), int(ex_b.shape[0])))
+    n_pairs = int((idx_a if idx_a is not None else idx_b if idx_b is not None else ex_a).shape[0])
+    idx_a, idx_b = _index(rt, idx_a, n_pairs, "idx_a"), _index(rt, idx_b, n_pairs, "idx_b")
+    with rt.lock, rt.on_stream():
+        out = rt.empty((n_pairs, 2))
+        _hip.check(rt.lib.wh_lsf_distortion(rt.ctx, rt.stream(), rt.ptr(ex_a), int(ex_a.shape[0]), _ld(ex_a), rt.ptr(ex_b),
+                                            int(ex_b.shape[0]), _ld(ex_b), p, rt.ptr(idx_a), rt.ptr(idx_b), n_pairs,
+                                            _dp(bin_table(int(k_bins))), int(k_bins), rt.ptr(out)))
+    return out
+
+
+def distortion_db(torch, g, s1, s2, k_bins, gain=True):
+    """The log-spectral distortion in dB from the gain difference g = log E_a - log E_b and the kernel's two sums (torch
+    or NumPy: ``torch`` is the module the arrays belong to).  The envelope is S = E / A2, so
+    ln S_a - ln S_b = g - ln(A2_a / A2_b) = g - t: the gain enters with the OPPOSITE sign of t.  Per pair,
+        gain=True:   c sqrt(max(0, mean_k (g - t)^2))      = c sqrt(max(0, g^2 - 2 g s1 / K + s2 / K))
+        gain=False:  c sqrt(max(0, var_k t))               = c sqrt(max(0, s2 / K - (s1 / K)^2))
+    with c = 10 / ln 10: the RMS over the bins of the dB difference, and the same with the best constant gain taken out
+    (the distortion of the spectral SHAPE)."""
+    m1, m2 = s1 / k_bins, s2 / k_bins
+    v = (g * g - 2.0 * g * m1 + m2) if gain else (m2 - m1 * m1)
+    return LSD_SCALE * torch.sqrt(torch.maximum(v, torch.zeros_like(v)))
+
+
+def distortion_device(rt, rows_a, rows_b, fft_size, idx_a=None, idx_b=None, gain=True):
+    """The log-spectral distortion in dB of pairs of rows [log E, w_1 .. w_p] (radians): [n_pairs], the RMS over the
+    fft_size // 2 + 1 bins of 10 log10(S_a / S_b) of the two all-pole envelopes, neither of which is written
+    (wh_lsf_distortion).  Pair n is row idx_a[n] of rows_a against row idx_b[n] of rows_b, or row n where an index is
+    None.  ``gain=False`` leaves the best constant gain out.  The sign of the cross term: distortion_db."""
+    k_bins = check_fft_size(fft_size, "lsf_distortion")
+    _check_rows(rt, "rows_a", rows_a, "lsf_distortion", 3)
+    _check_rows(rt, "rows_b", rows_b, "lsf_distortion", 3)
+    torch = rt.torch
+    with rt.lock, rt.on_stream():
+        # the kernel takes rows of p + 1 columns and does not read column 0: the cosines go into columns 1 .. p of a
+        # tensor whose column 0 is left as it is allocated
+        ex_a, ex_b = rt.empty(tuple(rows_a.shape)), rt.empty(tuple(rows_b.shape))
+        torch.cos(rows_a[:, 1:], out=ex_a[:, 1:])
+        torch.cos(rows_b[:, 1:], out=ex_b[:, 1:])
+        s = distortion_sums_device(rt, ex_a, ex_b, k_bins, idx_a, idx_b)
+        ga = rows_a[:, 0] if idx_a is None else _gather(torch, rows_a[:, 0], idx_a)
+        gb = rows_b[:, 0] if idx_b is None else _gather(torch, rows_b[:, 0], idx_b)
+        return distortion_db(torch, ga - gb, s[:, 0], s[:, 1], k_bins, gain)
+
+
+def _gather(torch, col, idx):
+    """col[idx] with NaN where an index is outside the column (the kernel's answer for such a pair)."""
+    n = int(col.shape[0])
+    ok = (idx >= 0) & (idx < n)
+    if n == 0:
+        return torch.full(idx.shape, float("nan"), dtype=col.dtype, device=col.device)
+    v = col.index_select(0, torch.where(ok, idx, torch.zeros_like(idx)))
+    return torch.where(ok, v, torch.full_like(v, float("nan")))
 
 
 # ---- NumPy forms (World.encode_lsf / decode_lsf / encode_lpc) ---------------------------------------------------------
@@ -215,6 +325,18 @@ def decode_lsf(lsf, fft_size, min_gap=0.0):
     _check_host_rows(lsf, "decode_lsf", 3)
     check_order(np.shape(lsf)[1] - 1, "decode_lsf")
     return _on_device(ilsf_device, lsf, int(fft_size), min_gap)
+
+
+def lsf_distortion(lsf_a, lsf_b, fft_size, gain=True):
+    """(N, p + 1) rows against (N, p + 1) rows -> (N,) log-spectral distortion in dB, frame by frame."""
+    check_fft_size(fft_size, "lsf_distortion")
+    _check_host_rows(lsf_a, "lsf_distortion", 3)
+    _check_host_rows(lsf_b, "lsf_distortion", 3)
+    if np.shape(lsf_a) != np.shape(lsf_b):
+        raise ValueError("lsf_distortion: rows of shape %s against %s" % (np.shape(lsf_a), np.shape(lsf_b)))
+    check_order(np.shape(lsf_a)[1] - 1, "lsf_distortion")
+    return _on_device(lambda rt, a: distortion_device(rt, a, rt.to_device(np.ascontiguousarray(lsf_b, dtype=np.float64)),
+                                                      int(fft_size), gain=gain), lsf_a)
 
 
 def encode_lpc(spec, order=24):

@@ -521,16 +521,18 @@ class World(object):
 
     # ---- joint-density GMM voice conversion (not in the reference's class; world/gmm.py) ----------------------------
     @_hip.serialised
-    def fit_conversion(self, dats_a, dats_b, n_components=8, n0=40, n_iter=20, devices=None, **kw):
+    def fit_conversion(self, dats_a, dats_b, n_components=8, n0=40, n_iter=20, devices=None, lsf_order=None, **kw):
         """A conversion model from parallel utterances: encode() dicts of a source speaker and of a target speaker, pair
         u the same sentence.  The pairs are aligned (align_batch's warping over mel-cepstra), the static + delta rows of
         the mel-cepstral coefficients 1 .. n0-1 of both sides are joined along the paths, and a mixture of
         ``n_components`` full-covariance Gaussians is fitted by ``n_iter`` EM iterations on the device
-        (world.gmm.fit_device; ``kw``: reg_covar, seed, init, radius, windows, ...).  Returns a world.gmm.JointGMM."""
+        (world.gmm.fit_device; ``kw``: reg_covar, seed, init, radius, windows, ...).  Returns a world.gmm.JointGMM.
+        ``lsf_order`` = p (even, <= 40): the same over the p angles of line spectral frequencies (encode_lsf's rows, the
+        gain dropped) instead of the mel-cepstrum — at any sampling rate; convert_voice follows the model's kind."""
         from .gmm import fit_conversion_dicts
         if devices is not None:
             raise NotImplementedError("fit_conversion(devices=...): run one WorldBatch per device instead")
-        return fit_conversion_dicts(dats_a, dats_b, n_components, n0, n_iter, **kw)
+        return fit_conversion_dicts(dats_a, dats_b, n_components, n0, n_iter, lsf_order=lsf_order, **kw)
 
     @_hip.serialised
     def convert_voice(self, dat, model, mode="mlpg", devices=None, **kw):
@@ -648,6 +650,15 @@ class World(object):
         (radians) first repairs rows that are out of order or closer than that (world/lsf.py)."""
         from . import lsf as _lsf
         return _lsf.decode_lsf(lsf, fft_size, min_gap)
+
+    def lsf_distortion(self, lsf_a, lsf_b, fft_size, gain=True, devices=None):
+        """(N, p + 1) rows of encode_lsf against (N, p + 1) rows -> (N,) the log-spectral distortion in dB of the two
+        all-pole envelopes on fft_size / 2 + 1 bins, frame by frame, computed from the rows without either envelope
+        (world.lsf.distortion_device).  ``gain=False`` leaves the best constant gain out: the spectral shape alone."""
+        from . import lsf as _lsf
+        if devices is not None:
+            raise NotImplementedError("lsf_distortion(devices=...): run one WorldBatch per device instead")
+        return _lsf.lsf_distortion(lsf_a, lsf_b, fft_size, gain)
 
     def encode_lpc(self, spec, order=24):
         """(N, D) power spectrogram -> (a (N, order + 1) with a[:, 0] = 1, the prediction-error gain E (N,), the
