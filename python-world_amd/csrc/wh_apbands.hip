@@ -103,16 +103,8 @@ extern "C" int wh_aperiodicity_from_bands(wh_ctx* ctx, void* stream, int64_t n_f
   if (groups > 0x7fffffffLL) return wh::fail_msg("wh_aperiodicity_from_bands", "too many frames for one launch");
   const wh::ApAxis ax = wh::ap_axis(fs, nap, frequency_interval, k_bins);
   const bool vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-  {
-    wh::KernelTimer _kt(ctx, st, "ap_from_bands_kernel");
-    if (vec)
-      hipLaunchKernelGGL(ap_from_bands_kernel<true>, dim3((unsigned)groups), dim3(kApThreads), 0, st, coarse, gate, out,
-                         (long long)n_frames, k_bins, ax);
-    else
-      hipLaunchKernelGGL(ap_from_bands_kernel<false>, dim3((unsigned)groups), dim3(kApThreads), 0, st, coarse, gate, out,
-                         (long long)n_frames, k_bins, ax);
-  }
-  WH_LAUNCH_CHECK("ap_from_bands_kernel");
+  WH_LAUNCH(ctx, st, "ap_from_bands_kernel", vec ? ap_from_bands_kernel<true> : ap_from_bands_kernel<false>,
+            dim3((unsigned)groups), dim3(kApThreads), 0, coarse, gate, out, n_frames, k_bins, ax);
   return 0;
 }
 
@@ -125,7 +117,7 @@ extern "C" int wh_aperiodicity_gate(wh_ctx* ctx, void* stream, int64_t n_frames,
   if (!aperiodicity || !gate) return wh::fail_msg("wh_aperiodicity_gate", "null argument");
   hipStream_t st = (hipStream_t)stream;
   const long long blocks = (n_frames + 255) / 256;
-  { wh::KernelTimer _kt(ctx, st, "ap_gate_kernel"); hipLaunchKernelGGL(ap_gate_kernel, dim3((unsigned)blocks), dim3(256), 0, st, aperiodicity, gate, (long long)n_frames, k_bins); }
-  WH_LAUNCH_CHECK("ap_gate_kernel");
+  WH_LAUNCH(ctx, st, "ap_gate_kernel", ap_gate_kernel, dim3((unsigned)blocks), dim3(256), 0, aperiodicity, gate,
+            n_frames, k_bins);
   return 0;
 }

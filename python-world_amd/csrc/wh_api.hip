@@ -38,10 +38,10 @@ void set_error(const std::string& msg) { g_last_error = msg; }
 int fail(const char* where, hipError_t e) {
   g_last_error = std::string(where) + ": " + hipGetErrorString(e);
   // The runtime keeps the error of a failed call (an allocation that did not fit, say) as its "last error" until somebody
-  // reads it — and every launch check of this library reads it (hipGetLastError behind a launch): left standing, the NEXT,
+  // reads it — and every launch of this library reads it (wh::launch, behind the kernel): left standing, the NEXT,
   // perfectly ordinary call reported it as its own ("wh_batch_create: out of memory" after a workspace that could not be
   // allocated; tools/oom_probe.py).  Reported once, here, and cleared.
-  (void)hipGetLastError();
+  clear_runtime_error();
   return (int)e == 0 ? -1 : (int)e;
 }
 int fail_msg(const char* where, const char* msg) {
@@ -312,8 +312,8 @@ int wh_bounds_selftest(wh_ctx* ctx, void* stream) {
 #if defined(WH_BOUNDS) && WH_BOUNDS
   WH_ENTER(ctx);
   if (int rc = wh::ws_reserve(ctx, 64)) return rc;
-  hipLaunchKernelGGL(bounds_selftest_kernel, dim3(1), dim3(4), 0, (hipStream_t)stream, reinterpret_cast<double*>(ctx->ws));
-  WH_LAUNCH_CHECK("bounds_selftest_kernel");
+  WH_LAUNCH_UNTIMED((hipStream_t)stream, "bounds_selftest_kernel", bounds_selftest_kernel, dim3(1), dim3(4), 0,
+                    reinterpret_cast<double*>(ctx->ws));
   return 0;
 #else
   return wh::fail_msg("wh_bounds_selftest", "not a bounds build");
@@ -345,9 +345,8 @@ int wh_math_probe(wh_ctx* ctx, void* stream, int which, const double* in, double
   if (n == 0) return 0;
   const double* d_mt = nullptr;
   if (int rc = wh::math_table(ctx, &d_mt)) return rc;
-  hipLaunchKernelGGL(math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, which, in, out, (long long)n,
-                     d_mt, (const double2*)ctx->d_twiddle);
-  WH_LAUNCH_CHECK("math_probe_kernel");
+  WH_LAUNCH_UNTIMED((hipStream_t)stream, "math_probe_kernel", math_probe_kernel, dim3((unsigned)((n + 255) / 256)),
+                    dim3(256), 0, which, in, out, n, d_mt, ctx->d_twiddle);
   return 0;
 }
 
@@ -381,16 +380,14 @@ int wh_fft_probe(wh_ctx* ctx, void* stream, int n, int gt, int snt, int inverse,
   const hipStream_t st = (hipStream_t)stream;
   const double2* a = reinterpret_cast<const double2*>(in);
   double2* o = reinterpret_cast<double2*>(out);
-  auto launch = [&](auto kernel, int g, int t) {
-    const int per = t / g;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((count + per - 1) / per)), dim3(t), sizeof(double2) * 512 * per, st, a, o,
-                       (const double2*)ctx->d_twiddle, (long long)count, inverse);
-  };
-  if (gt == 64 && snt == 64) launch(fft_probe_kernel<64, 64>, 64, 64);
-  else if (gt == 128 && snt == 256) launch(fft_probe_kernel<128, 256>, 128, 256);
-  else if (gt == 256 && snt == 256) launch(fft_probe_kernel<256, 256>, 256, 256);
-  else return wh::fail_msg("wh_fft_probe", "shape not built (gt, snt): (64, 64), (128, 256), (256, 256)");
-  WH_LAUNCH_CHECK("fft_probe_kernel");
+  const auto kernel = gt == 64 && snt == 64     ? fft_probe_kernel<64, 64>
+                      : gt == 128 && snt == 256 ? fft_probe_kernel<128, 256>
+                      : gt == 256 && snt == 256 ? fft_probe_kernel<256, 256>
+                                                : nullptr;
+  if (!kernel) return wh::fail_msg("wh_fft_probe", "shape not built (gt, snt): (64, 64), (128, 256), (256, 256)");
+  const int per = snt / gt;
+  WH_LAUNCH_UNTIMED(st, "fft_probe_kernel", kernel, dim3((unsigned)((count + per - 1) / per)), dim3(snt),
+                    sizeof(double2) * 512 * per, a, o, ctx->d_twiddle, count, inverse);
   return 0;
 }
 
@@ -451,8 +448,8 @@ int wh_flags_post(wh_ctx* ctx, void* stream, int discard) {
   }
   int32_t* d_mirror = nullptr;
   WH_CHECK(hipHostGetDevicePointer((void**)&d_mirror, (void*)ctx->h_flag_cum, 0));
-  hipLaunchKernelGGL(flags_post_kernel, dim3(1), dim3(64), 0, st, ctx->d_flags, ctx->d_flag_cum, d_mirror);
-  WH_LAUNCH_CHECK("flags_post_kernel");
+  WH_LAUNCH_UNTIMED(st, "flags_post_kernel", flags_post_kernel, dim3(1), dim3(64), 0, ctx->d_flags, ctx->d_flag_cum,
+                    d_mirror);
   return 0;
 }
 
@@ -537,11 +534,9 @@ int wh_copy_mapped(wh_ctx* ctx, void* stream, void* dst, const void* src, size_t
   int blocks = max_blocks > 0 ? max_blocks : 64;
   const size_t need = (n16 + 255) / 256;
   if ((size_t)blocks > need) blocks = need ? (int)need : 1;
-  wh::KernelTimer t(ctx, st, "copy_mapped_kernel");
-  copy_mapped_kernel<<<blocks, 256, 0, st>>>((double2*)dst, (const double2*)src, n16,
-                                            tail ? (double*)dst + 2 * n16 : nullptr,
-                                            tail ? (const double*)src + 2 * n16 : nullptr);
-  WH_LAUNCH_CHECK("copy_mapped_kernel");
+  WH_LAUNCH(ctx, st, "copy_mapped_kernel", copy_mapped_kernel, dim3(blocks), dim3(256), 0, (double2*)dst,
+            (const double2*)src, n16, tail ? (double*)dst + 2 * n16 : nullptr,
+            tail ? (const double*)src + 2 * n16 : nullptr);
   return 0;
 }
 
@@ -570,19 +565,21 @@ int wh_batch_create(wh_ctx* ctx, int n_utt, const int64_t* h_x_off, const int64_
   if (e == hipSuccess) e = hipMalloc((void**)&b->d_frame_utt, (size_t)(b->total_frames > 0 ? b->total_frames : 1) * sizeof(int32_t));
   if (e == hipSuccess) e = hipMemcpy(b->d_x_off, h_x_off, ob, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(b->d_frame_off, h_frame_off, ob, hipMemcpyHostToDevice);
+  int rc = 0;
   if (e == hipSuccess && b->total_frames > 0) {
     int blocks = (int)((b->total_frames + 255) / 256);
     if (blocks > 4096) blocks = 4096;
-    frame_utt_kernel<<<blocks, 256>>>(b->d_frame_off, n_utt, b->total_frames, b->d_frame_utt);
-    e = hipGetLastError();
+    rc = wh::launch_untimed(nullptr, "frame_utt_kernel", frame_utt_kernel, dim3(blocks), dim3(256), 0, b->d_frame_off,
+                            n_utt, b->total_frames, b->d_frame_utt);
     // The descriptor is complete when this call returns (it has no stream argument: whichever stream uses the batch next
     // finds the table written).  Only the null stream is waited for — a device-wide wait here made every batch created
     // while another context's kernels were running (a second pipeline on its own non-blocking stream) wait for them.
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (!rc) e = hipStreamSynchronize(nullptr);
   }
-  if (e != hipSuccess) {
+  if (!rc && e != hipSuccess) rc = wh::fail("wh_batch_create", e);
+  if (rc) {
     wh_batch_destroy(b);
-    return wh::fail("wh_batch_create", e);
+    return rc;
   }
   *out = b;
   return 0;

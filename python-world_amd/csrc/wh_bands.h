@@ -199,14 +199,10 @@ inline int launch_band_events(wh_ctx* ctx, hipStream_t st, const BandJob* d_jobs
   const size_t lds = sizeof(double) * (((max_lb + 1) & ~1) + kBandPlanes * band_plane_len(kBandTileR + 2 + max_lb) +
                                        kBandTileR + 2) + 64;
   if (int rc = allow_lds(&band_events_kernel<true>, lds)) return rc;
-  { KernelTimer _kt(ctx, st, "band_events_kernel"); hipLaunchKernelGGL(band_events_kernel<true>, dim3(nb, n_utt, nseg), dim3(256), lds, st, d_jobs, pad, d_taps, d_tap_off, d_tap_len, d_bias, nb, d_flag); }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail("band_events_kernel", e);
-  if (nseg > 1) {
-    { KernelTimer _kt(ctx, st, "band_concat_kernel"); hipLaunchKernelGGL(band_concat_kernel, dim3(nb * n_utt), dim3(256), 0, st, d_jobs, nseg, d_flag); }
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail("band_concat_kernel", e);
-  }
+  WH_LAUNCH(ctx, st, "band_events_kernel", band_events_kernel<true>, dim3(nb, n_utt, nseg), dim3(256), lds, d_jobs, pad,
+            d_taps, d_tap_off, d_tap_len, d_bias, nb, d_flag);
+  if (nseg > 1)
+    WH_LAUNCH(ctx, st, "band_concat_kernel", band_concat_kernel, dim3(nb * n_utt), dim3(256), 0, d_jobs, nseg, d_flag);
   return 0;
 }
 
@@ -446,17 +442,15 @@ inline int launch_band_events_ols(wh_ctx* ctx, hipStream_t st, const BandJob* d_
                                   const int32_t* d_half, const int64_t* d_tile_off, int64_t max_tiles, double2* d_tspec,
                                   double* d_tre, double2* d_zspec, int32_t* d_flag) {
   const size_t lds_fft = sizeof(double) * (kOlsN + 2);
-  { KernelTimer _kt(ctx, st, "band_taps_fft_kernel"); hipLaunchKernelGGL(band_taps_fft_kernel, dim3(nb), dim3(256), lds_fft, st, d_taps, d_tap_off, d_tap_len, ctx->d_twiddle, d_tspec, d_tre); }
-  { KernelTimer _kt(ctx, st, "band_tile_fft_kernel"); hipLaunchKernelGGL(band_tile_fft_kernel, dim3((unsigned)max_tiles, n_utt), dim3(256), lds_fft, st, d_jobs, nb, pad, H, d_tile_off, ctx->d_twiddle, d_zspec); }
+  WH_LAUNCH(ctx, st, "band_taps_fft_kernel", band_taps_fft_kernel, dim3(nb), dim3(256), lds_fft, d_taps, d_tap_off,
+            d_tap_len, ctx->d_twiddle, d_tspec, d_tre);
+  WH_LAUNCH(ctx, st, "band_tile_fft_kernel", band_tile_fft_kernel, dim3((unsigned)max_tiles, n_utt), dim3(256), lds_fft,
+            d_jobs, nb, pad, H, d_tile_off, ctx->d_twiddle, d_zspec);
   const size_t lds = sizeof(double2) * (kOlsN / 2 + 2) + 64;
-  {
-    KernelTimer _kt(ctx, st, "band_events_kernel");
-    const int n_xcd = n_utt >= 8 ? 8 : 1;
-    const unsigned u8 = (unsigned)(((n_utt + n_xcd - 1) / n_xcd) * n_xcd);
-    hipLaunchKernelGGL(band_events_ols_kernel<1>, dim3(u8 * nb), dim3(256), lds, st, d_jobs, nb, n_utt, n_xcd, H, d_half, d_tre, d_zspec, d_tile_off, ctx->d_twiddle, d_flag);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail("band_events_ols_kernel", e);
+  const int n_xcd = n_utt >= 8 ? 8 : 1;
+  const unsigned u8 = (unsigned)(((n_utt + n_xcd - 1) / n_xcd) * n_xcd);
+  WH_LAUNCH(ctx, st, "band_events_kernel", band_events_ols_kernel<1>, dim3(u8 * nb), dim3(256), lds, d_jobs, nb, n_utt,
+            n_xcd, H, d_half, d_tre, d_zspec, d_tile_off, ctx->d_twiddle, d_flag);
   return 0;
 }
 

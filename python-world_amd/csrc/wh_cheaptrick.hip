@@ -240,10 +240,9 @@ int launch(wh_ctx* ctx, hipStream_t st, const wh_batch* b, const double* x, cons
   const size_t lds = sizeof(double) * ((N + 2) + (N / 2 + 2) + 32);
   const double low = fs * 3.0 / (N - 3.0);
   if (int rc = wh::allow_lds(&cheaptrick_kernel<N>, lds)) return rc;
-  { wh::KernelTimer _kt(ctx, st, "cheaptrick_kernel"); hipLaunchKernelGGL(cheaptrick_kernel<N>, dim3((unsigned)wh::xcd_grid(b->total_frames)), dim3(ft_ct(N)), lds, st, x, b->d_x_off,
-                     b->d_frame_utt, tp, f0, vuv, fs, q1, low, ctx->d_twiddle, spec,
-                     reinterpret_cast<double2*>(ps), (long long)b->total_frames); }
-  WH_LAUNCH_CHECK("cheaptrick_kernel");
+  WH_LAUNCH(ctx, st, "cheaptrick_kernel", cheaptrick_kernel<N>, dim3((unsigned)wh::xcd_grid(b->total_frames)),
+            dim3(ft_ct(N)), lds, x, b->d_x_off, b->d_frame_utt, tp, f0, vuv, fs, q1, low, ctx->d_twiddle, spec,
+            reinterpret_cast<double2*>(ps), b->total_frames);
   return 0;
 }
 

@@ -432,9 +432,9 @@ template <int NLT>
 int launch_lt(const D4cCall& a) {
   const size_t lds = sizeof(double) * love_lds_doubles(NLT);
   if (int rc = wh::allow_lds(&love_train_kernel<NLT>, lds)) return rc;
-  { wh::KernelTimer _kt(a.ctx, a.st, "love_train_kernel"); hipLaunchKernelGGL(love_train_kernel<NLT>, dim3((unsigned)wh::xcd_grid(a.b->total_frames)), dim3(ft_love(NLT)), lds, a.st, a.x, a.b->d_x_off,
-                     a.b->d_frame_utt, a.tp, a.f0, a.vuv, a.fs, a.thr, a.ctx->d_twiddle, a.gate, (long long)a.b->total_frames); }
-  WH_LAUNCH_CHECK("love_train_kernel");
+  WH_LAUNCH(a.ctx, a.st, "love_train_kernel", love_train_kernel<NLT>, dim3((unsigned)wh::xcd_grid(a.b->total_frames)),
+            dim3(ft_love(NLT)), lds, a.x, a.b->d_x_off, a.b->d_frame_utt, a.tp, a.f0, a.vuv, a.fs, a.thr,
+            a.ctx->d_twiddle, a.gate, a.b->total_frames);
   return 0;
 }
 
@@ -442,10 +442,10 @@ template <int N, bool FUSED>
 int launch_main(const D4cCall& a) {
   const size_t lds = sizeof(double) * d4c_lds_doubles(N);
   if (int rc = wh::allow_lds(&d4c_kernel<N, FUSED>, lds)) return rc;
-  { wh::KernelTimer _kt(a.ctx, a.st, "d4c_kernel"); hipLaunchKernelGGL((d4c_kernel<N, FUSED>), dim3((unsigned)wh::xcd_grid(a.b->total_frames)), dim3(ft_of(N)), lds, a.st, a.x, a.b->d_x_off,
-                     a.b->d_frame_utt, a.tp, a.f0, a.vuv, a.gate, a.thr, a.fs, a.nap, a.interval, a.win, a.wlen, a.ctx->d_twiddle, a.k_spec, a.out,
-                     a.coarse, (long long)a.b->total_frames, d4c_launch_const(a.fs, N, a.wlen, a.interval, a.nap)); }
-  WH_LAUNCH_CHECK("d4c_kernel");
+  WH_LAUNCH(a.ctx, a.st, "d4c_kernel", d4c_kernel<N, FUSED>, dim3((unsigned)wh::xcd_grid(a.b->total_frames)),
+            dim3(ft_of(N)), lds, a.x, a.b->d_x_off, a.b->d_frame_utt, a.tp, a.f0, a.vuv, a.gate, a.thr, a.fs, a.nap,
+            a.interval, a.win, a.wlen, a.ctx->d_twiddle, a.k_spec, a.out, a.coarse, a.b->total_frames,
+            d4c_launch_const(a.fs, N, a.wlen, a.interval, a.nap));
   return 0;
 }
 

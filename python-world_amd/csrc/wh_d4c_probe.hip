@@ -104,9 +104,8 @@ template <int N>
 int launch_select_probe(hipStream_t st, int layout, int m, const double* vals, double* out, long long count) {
   const size_t lds = sizeof(double) * d4c_lds_front(N);
   if (int rc = wh::allow_lds(&d4c_select_probe_kernel<N>, lds)) return rc;
-  hipLaunchKernelGGL(d4c_select_probe_kernel<N>, dim3((unsigned)count), dim3(ft_of(N)), lds, st, vals, out, layout, m, count);
-  WH_LAUNCH_CHECK("d4c_select_probe_kernel");
-  return 0;
+  return wh::launch_untimed(st, "d4c_select_probe_kernel", d4c_select_probe_kernel<N>, dim3((unsigned)count),
+                            dim3(ft_of(N)), lds, vals, out, layout, m, count);
 }
 
 template <int N>
@@ -114,9 +113,8 @@ int launch_runs_probe(hipStream_t st, int which, double fs, const double* f0, co
                       long long count) {
   const size_t lds = sizeof(double) * d4c_lds_front(N);
   if (int rc = wh::allow_lds(&d4c_runs_probe_kernel<N>, lds)) return rc;
-  hipLaunchKernelGGL(d4c_runs_probe_kernel<N>, dim3((unsigned)count), dim3(ft_of(N)), lds, st, in, out, f0, rh, which, fs, count);
-  WH_LAUNCH_CHECK("d4c_runs_probe_kernel");
-  return 0;
+  return wh::launch_untimed(st, "d4c_runs_probe_kernel", d4c_runs_probe_kernel<N>, dim3((unsigned)count),
+                            dim3(ft_of(N)), lds, in, out, f0, rh, which, fs, count);
 }
 
 }  // namespace

@@ -552,14 +552,11 @@ extern "C" int wh_dio(wh_ctx* ctx, void* stream, const wh_batch* b, const double
   if (!(rad < 0.9999)) warm = 1 << 30;  // unstable / unknown: fall back to a fully serial pass per lane
   const int chunks = (int)((max_len + kChunk - 1) / kChunk);
   dim3 gi((chunks + 63) / 64, B);
-  { wh::KernelTimer _kt(ctx, st, "iir_fwd_kernel"); hipLaunchKernelGGL(iir_fwd_kernel, gi, dim3(64), 0, st, x, d_meta, coef, warm, d_tmp); }
-  WH_LAUNCH_CHECK("iir_fwd_kernel");
-  { wh::KernelTimer _kt(ctx, st, "iir_bwd_kernel"); hipLaunchKernelGGL(iir_bwd_kernel, gi, dim3(64), 0, st, d_meta, coef, warm, r, d_tmp, d_y); }
-  WH_LAUNCH_CHECK("iir_bwd_kernel");
+  WH_LAUNCH(ctx, st, "iir_fwd_kernel", iir_fwd_kernel, gi, dim3(64), 0, x, d_meta, coef, warm, d_tmp);
+  WH_LAUNCH(ctx, st, "iir_bwd_kernel", iir_bwd_kernel, gi, dim3(64), 0, d_meta, coef, warm, r, d_tmp, d_y);
   // ---- low-cut + band events ----------------------------------------------------------------------
-  { wh::KernelTimer _kt(ctx, st, "lowcut_kernel"); hipLaunchKernelGGL(lowcut_kernel, dim3((unsigned)((max_ylen + 2 * pad + 255) / 256), B), dim3(256), sizeof(double) * (256 + 2 * lowcut_half), st, d_meta, d_y,
-                     d_lc, lowcut_half, pad, d_z); }
-  WH_LAUNCH_CHECK("lowcut_kernel");
+  WH_LAUNCH(ctx, st, "lowcut_kernel", lowcut_kernel, dim3((unsigned)((max_ylen + 2 * pad + 255) / 256), B), dim3(256),
+            sizeof(double) * (256 + 2 * lowcut_half), d_meta, d_y, d_lc, lowcut_half, pad, d_z);
   {
     std::vector<wh::BandJob> jobs((size_t)B * n_bands);
     for (int u = 0; u < B; ++u)
@@ -580,21 +577,17 @@ extern "C" int wh_dio(wh_ctx* ctx, void* stream, const wh_batch* b, const double
                                       max_lb, ctx->d_flags + WH_FLAG_EVENT_OVERFLOW, kBandSegs))
     return rc;
   // ---- candidates, sort, contour ------------------------------------------------------------------
-  { wh::KernelTimer _kt(ctx, st, "cand_kernel"); hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((max_nf + 255) / 256), n_bands, B), dim3(256), 0, st, d_meta, tp, d_e,
-                     d_cnt, d_bf, n_bands, fs_d, f0_floor, f0_ceil, d_raw, d_stab); }
-  WH_LAUNCH_CHECK("cand_kernel");
-  { wh::KernelTimer _kt(ctx, st, "sort_kernel"); hipLaunchKernelGGL(sort_kernel, dim3((unsigned)((max_nf + 255) / 256), B), dim3(256), 0, st, d_meta, n_bands, d_raw,
-                     d_stab, d_sorted, cand_out); }
-  WH_LAUNCH_CHECK("sort_kernel");
+  WH_LAUNCH(ctx, st, "cand_kernel", cand_kernel, dim3((unsigned)((max_nf + 255) / 256), n_bands, B), dim3(256), 0,
+            d_meta, tp, d_e, d_cnt, d_bf, n_bands, fs_d, f0_floor, f0_ceil, d_raw, d_stab);
+  WH_LAUNCH(ctx, st, "sort_kernel", sort_kernel, dim3((unsigned)((max_nf + 255) / 256), B), dim3(256), 0, d_meta,
+            n_bands, d_raw, d_stab, d_sorted, cand_out);
   {
     // candidate rows + contour in LDS when the longest utterance fits (see contour_kernel)
     const size_t want = sizeof(double) * (size_t)(n_bands + 1) * (size_t)max_nf;
     const size_t lds = want <= 150 * 1024 ? want : 0;
     if (int rc = wh::allow_lds(&contour_kernel, lds)) return rc;
-    wh::KernelTimer _kt(ctx, st, "contour_kernel");
-    hipLaunchKernelGGL(contour_kernel, dim3(B), dim3(256), lds, st, d_meta, B, n_bands, frame_period_ms, f0_floor,
-                       allowed_range, d_sorted, d_work, f0_out, vuv_out, (int64_t)(lds / sizeof(double)));
+    WH_LAUNCH(ctx, st, "contour_kernel", contour_kernel, dim3(B), dim3(256), lds, d_meta, B, n_bands, frame_period_ms,
+              f0_floor, allowed_range, d_sorted, d_work, f0_out, vuv_out, lds / sizeof(double));
   }
-  WH_LAUNCH_CHECK("contour_kernel");
   return 0;
 }

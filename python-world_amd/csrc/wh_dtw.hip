@@ -281,14 +281,10 @@ __global__ __launch_bounds__(WH_BLOCK) void dtw_reverse_kernel(const int64_t* __
   }
 }
 
-template <int DP>
-void dtw_launch(wh_ctx* ctx, hipStream_t st, int n, const int64_t* pairs, const double* xa, long long lda, long long len_a,
-                const double* xb, long long ldb, long long len_b, int d, long long radius, uint32_t* bp, long long bp_words,
-                double* line, long long line_len, double* total, double* acc, long long acc_len) {
-  wh::KernelTimer _kt(ctx, st, "dtw_recurrence_kernel");
-  hipLaunchKernelGGL(dtw_recurrence_kernel<DP>, dim3((unsigned)n), dim3(WH_WAVE), 0, st, pairs, n, xa, lda, len_a, xb, ldb,
-                     len_b, d, radius, bp, bp_words, line, line_len, total, acc, acc_len);
-}
+// dtw_recurrence_kernel<DP> by DP / 8 - 1: the feature dimension padded to a multiple of 8
+decltype(&dtw_recurrence_kernel<8>) const kDtwRecurrence[8] = {
+    dtw_recurrence_kernel<8>,  dtw_recurrence_kernel<16>, dtw_recurrence_kernel<24>, dtw_recurrence_kernel<32>,
+    dtw_recurrence_kernel<40>, dtw_recurrence_kernel<48>, dtw_recurrence_kernel<56>, dtw_recurrence_kernel<64>};
 
 }  // namespace
 
@@ -338,26 +334,13 @@ extern "C" int wh_dtw(wh_ctx* ctx, void* stream, const wh_batch* a, const wh_bat
   uint32_t* bp = reinterpret_cast<uint32_t*>(line + line_len);
   const long long len_a = (a->total_frames - 1) * lda + d, len_b = (b->total_frames - 1) * ldb + d;
   const long long path_total = h_path_off[n];
-  switch ((d + 7) / 8) {
-#define WH_DTW_CASE(DP)                                                                                                   \
-  case DP / 8:                                                                                                            \
-    dtw_launch<DP>(ctx, st, n, d_pairs, xa, lda, len_a, xb, ldb, len_b, d, radius, bp, bp_words, line, line_len, total_cost, \
-                   acc_out, acc_len);                                                                                     \
-    break;
-    WH_DTW_CASE(8)
-    WH_DTW_CASE(16)
-    WH_DTW_CASE(24)
-    WH_DTW_CASE(32)
-    WH_DTW_CASE(40)
-    WH_DTW_CASE(48)
-    WH_DTW_CASE(56)
-    WH_DTW_CASE(64)
-#undef WH_DTW_CASE
-  }
-  WH_LAUNCH_CHECK("dtw_recurrence_kernel");
-  { wh::KernelTimer _kt(ctx, st, "dtw_backtrack_kernel"); hipLaunchKernelGGL(dtw_backtrack_kernel, dim3((unsigned)((n + WH_WAVE - 1) / WH_WAVE)), dim3(WH_WAVE), 0, st, d_pairs, n, bp, bp_words, path_a, path_b, path_total, path_len, map_a2b, (long long)a->total_frames, map_b2a, (long long)b->total_frames); }
-  WH_LAUNCH_CHECK("dtw_backtrack_kernel");
-  { wh::KernelTimer _kt(ctx, st, "dtw_reverse_kernel"); hipLaunchKernelGGL(dtw_reverse_kernel, dim3((unsigned)n), dim3(WH_BLOCK), 0, st, d_pairs, n, path_a, path_b, path_total, path_len); }
-  WH_LAUNCH_CHECK("dtw_reverse_kernel");
+  WH_LAUNCH(ctx, st, "dtw_recurrence_kernel", kDtwRecurrence[(d + 7) / 8 - 1], dim3((unsigned)n), dim3(WH_WAVE), 0,
+            d_pairs, n, xa, lda, len_a, xb, ldb, len_b, d, radius, bp, bp_words, line, line_len, total_cost, acc_out,
+            acc_len);
+  WH_LAUNCH(ctx, st, "dtw_backtrack_kernel", dtw_backtrack_kernel, dim3((unsigned)((n + WH_WAVE - 1) / WH_WAVE)),
+            dim3(WH_WAVE), 0, d_pairs, n, bp, bp_words, path_a, path_b, path_total, path_len, map_a2b, a->total_frames,
+            map_b2a, b->total_frames);
+  WH_LAUNCH(ctx, st, "dtw_reverse_kernel", dtw_reverse_kernel, dim3((unsigned)n), dim3(WH_BLOCK), 0, d_pairs, n, path_a,
+            path_b, path_total, path_len);
   return 0;
 }

@@ -121,18 +121,12 @@ __global__ __launch_bounds__(256) void context_kernel(const double* __restrict__
   }
 }
 
-template <int PRO>
-int launch_epi(int epi, dim3 grid, hipStream_t st, const double* A, long long n_rows, int ka, long long lda, const double* P,
-               double pscale, const double* W, int kpad, int npad, int nw, double* out, long long ldo) {
-  switch (epi) {
-    case 0: hipLaunchKernelGGL((feature_matmul_kernel<PRO, 0>), grid, dim3(256), 0, st, A, n_rows, ka, lda, P, pscale, W, kpad, npad, nw, out, ldo); break;
-    case 1: hipLaunchKernelGGL((feature_matmul_kernel<PRO, 1>), grid, dim3(256), 0, st, A, n_rows, ka, lda, P, pscale, W, kpad, npad, nw, out, ldo); break;
-    case 2: hipLaunchKernelGGL((feature_matmul_kernel<PRO, 2>), grid, dim3(256), 0, st, A, n_rows, ka, lda, P, pscale, W, kpad, npad, nw, out, ldo); break;
-    case 3: hipLaunchKernelGGL((feature_matmul_kernel<PRO, 3>), grid, dim3(256), 0, st, A, n_rows, ka, lda, P, pscale, W, kpad, npad, nw, out, ldo); break;
-    default: return wh::fail_msg("wh_feature_matmul", "epilogue must be 0 (none), 1 (log), 2 (exp) or 3 (sqrt of the positive part)");
-  }
-  return 0;
-}
+// feature_matmul_kernel<prologue, epilogue>
+decltype(&feature_matmul_kernel<0, 0>) const kFeatKernels[3][4] = {
+    {feature_matmul_kernel<0, 0>, feature_matmul_kernel<0, 1>, feature_matmul_kernel<0, 2>, feature_matmul_kernel<0, 3>},
+    {feature_matmul_kernel<1, 0>, feature_matmul_kernel<1, 1>, feature_matmul_kernel<1, 2>, feature_matmul_kernel<1, 3>},
+    {feature_matmul_kernel<2, 0>, feature_matmul_kernel<2, 1>, feature_matmul_kernel<2, 2>, feature_matmul_kernel<2, 3>},
+};
 
 }  // namespace
 
@@ -165,18 +159,12 @@ extern "C" int wh_feature_matmul_tagged(wh_ctx* ctx, void* stream, const double*
     if (int rc = wh::persistent_upload(ctx, st, "feat.p." + std::to_string(ka), pv, &d_p)) return rc;
   }
   const dim3 grid((unsigned)((n_rows + kFeatRows - 1) / kFeatRows), (unsigned)((npad / 16 + kFeatNT - 1) / kFeatNT));
-  int rc;
-  {
-    wh::KernelTimer _kt(ctx, st, "feature_matmul_kernel");
-    switch (prologue) {
-      case 0: rc = launch_epi<0>(epilogue, grid, st, a, n_rows, ka, lda, d_p, pscale, d_w, kpad, npad, nw, out, ldo); break;
-      case 1: rc = launch_epi<1>(epilogue, grid, st, a, n_rows, ka, lda, d_p, pscale, d_w, kpad, npad, nw, out, ldo); break;
-      case 2: rc = launch_epi<2>(epilogue, grid, st, a, n_rows, ka, lda, d_p, pscale, d_w, kpad, npad, nw, out, ldo); break;
-      default: return wh::fail_msg("wh_feature_matmul", "prologue must be 0 (none), 1 (pre-emphasised power) or 2 (log)");
-    }
-  }
-  if (rc) return rc;
-  WH_LAUNCH_CHECK("feature_matmul_kernel");
+  if (prologue < 0 || prologue > 2)
+    return wh::fail_msg("wh_feature_matmul", "prologue must be 0 (none), 1 (pre-emphasised power) or 2 (log)");
+  if (epilogue < 0 || epilogue > 3)
+    return wh::fail_msg("wh_feature_matmul", "epilogue must be 0 (none), 1 (log), 2 (exp) or 3 (sqrt of the positive part)");
+  WH_LAUNCH(ctx, st, "feature_matmul_kernel", kFeatKernels[prologue][epilogue], grid, dim3(256), 0, a, n_rows, ka, lda,
+            d_p, pscale, d_w, kpad, npad, nw, out, ldo);
   return 0;
 }
 
@@ -192,7 +180,6 @@ extern "C" int wh_context_frames(wh_ctx* ctx, void* stream, const double* x, int
   if (n_rows <= 0) return 0;
   if (d < 1 || w < 0) return wh::fail_msg("wh_context_frames", "bad shape");
   hipStream_t st = (hipStream_t)stream;
-  { wh::KernelTimer _kt(ctx, st, "context_kernel"); hipLaunchKernelGGL(context_kernel, dim3((unsigned)n_rows), dim3(256), 0, st, x, (long long)n_rows, d, w, out); }
-  WH_LAUNCH_CHECK("context_kernel");
+  WH_LAUNCH(ctx, st, "context_kernel", context_kernel, dim3((unsigned)n_rows), dim3(256), 0, x, n_rows, d, w, out);
   return 0;
 }

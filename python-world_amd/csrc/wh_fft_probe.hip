@@ -61,10 +61,8 @@ int launch_probe(wh_ctx* ctx, hipStream_t st, const double* in, double* out, lon
   static_assert(lds <= 160 * 1024, "one workgroup's buffers must fit the CU's LDS");
   auto kernel = fft_engine_probe_kernel<KIND, N, NT, SNT, MAXR, INV>;
   if (int rc = wh::allow_lds(kernel, lds)) return rc;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((count + per - 1) / per)), dim3(SNT), lds, st, in, out,
-                     (const double2*)ctx->d_twiddle, count);
-  WH_LAUNCH_CHECK("fft_engine_probe_kernel");
-  return 0;
+  return wh::launch_untimed(st, "fft_engine_probe_kernel", kernel, dim3((unsigned)((count + per - 1) / per)), dim3(SNT),
+                            lds, in, out, ctx->d_twiddle, count);
 }
 
 }  // namespace
@@ -114,11 +112,18 @@ int wh_fft_engine_probe(wh_ctx* ctx, void* stream, int kind, int n, int nt, int 
   WH_ENTER(ctx);
   if (count == 0) return 0;
   const hipStream_t st = (hipStream_t)stream;
-#define WH_PROBE_CASE(K, N_, NT_, SNT_, MAXR_, INV_)                                                      \
-  if (kind == K && n == N_ && nt == NT_ && snt == SNT_ && maxr == MAXR_ && inverse == (INV_))             \
-    return launch_probe<K, N_, NT_, SNT_, MAXR_, (INV_) != 0>(ctx, st, in, out, (long long)count);
-  WH_PROBE_SHAPES(WH_PROBE_CASE)
-#undef WH_PROBE_CASE
+  static const struct {
+    int kind, n, nt, snt, maxr, inverse;
+    int (*launch)(wh_ctx*, hipStream_t, const double*, double*, long long);
+  } built[] = {
+#define WH_PROBE_ROW(K, N_, NT_, SNT_, MAXR_, INV_) \
+  {K, N_, NT_, SNT_, MAXR_, INV_, launch_probe<K, N_, NT_, SNT_, MAXR_, (INV_) != 0>},
+      WH_PROBE_SHAPES(WH_PROBE_ROW)
+#undef WH_PROBE_ROW
+  };
+  for (const auto& s : built)
+    if (kind == s.kind && n == s.n && nt == s.nt && snt == s.snt && maxr == s.maxr && inverse == s.inverse)
+      return s.launch(ctx, st, in, out, count);
   return wh::fail_msg("wh_fft_engine_probe", "shape (kind, n, nt, snt, maxr, inverse) not built: see WH_PROBE_SHAPES in csrc/wh_fft_probe.hip");
 }
 

@@ -371,14 +371,9 @@ extern "C" int wh_gmm_estep(wh_ctx* ctx, void* stream, const double* x, int64_t 
   const size_t lds = gmm_rows_lds(0, M);
   if (int rc = wh::allow_lds(gmm_rows_kernel<0>, lds)) return rc;
   const long long blocks = (n_rows + kGmmRowTile - 1) / kGmmRowTile;
-  {
-    wh::KernelTimer _kt(ctx, st, "gmm_estep_kernel");
-    hipLaunchKernelGGL(gmm_rows_kernel<0>, dim3((unsigned)blocks), dim3(256), lds, st, x, (long long)n_rows, (long long)ldx,
-                       (n_rows - 1) * ldx + d, d, d, M, mu, whiten, logc, (const double*)nullptr, (const int32_t*)nullptr,
-                       (const double*)nullptr, 0LL, 0LL, ll, (long long)ldl, ll ? (n_rows - 1) * ldl + M : 0LL, gamma,
-                       (long long)ldg, gamma ? (n_rows - 1) * ldg + M : 0LL, rowll, best);
-  }
-  WH_LAUNCH_CHECK("gmm_estep_kernel");
+  WH_LAUNCH(ctx, st, "gmm_estep_kernel", gmm_rows_kernel<0>, dim3((unsigned)blocks), dim3(256), lds, x, n_rows, ldx,
+            (n_rows - 1) * ldx + d, d, d, M, mu, whiten, logc, nullptr, nullptr, nullptr, 0LL, 0LL, ll, ldl,
+            ll ? (n_rows - 1) * ldl + M : 0LL, gamma, ldg, gamma ? (n_rows - 1) * ldg + M : 0LL, rowll, best);
   return 0;
 }
 
@@ -399,20 +394,12 @@ extern "C" int wh_gmm_stats(wh_ctx* ctx, void* stream, const double* x, int64_t 
   void* scratch = nullptr;
   if (int rc = wh::persistent_scratch(ctx, "gmm.partials", (size_t)len_p * sizeof(double), &scratch)) return rc;
   double* part = reinterpret_cast<double*>(scratch);
-  {
-    wh::KernelTimer _kt(ctx, st, "gmm_stats_kernel");
-    hipLaunchKernelGGL(gmm_stats_kernel, dim3((unsigned)M, (unsigned)splits), dim3(64 * kGmmStatsWaves), 0, st, x, (long long)n_rows,
-                       (long long)ldx, (n_rows - 1) * ldx + d, d, M, gamma, (long long)ldg, (n_rows - 1) * ldg + M, mu, part,
-                       len_p);
-  }
-  WH_LAUNCH_CHECK("gmm_stats_kernel");
-  {
-    wh::KernelTimer _kt(ctx, st, "gmm_combine_kernel");
-    const long long total = (long long)M * per;
-    hipLaunchKernelGGL(gmm_combine_kernel, dim3((unsigned)((total + WH_BLOCK - 1) / WH_BLOCK)), dim3(WH_BLOCK), 0, st, part,
-                       len_p, splits, d, M, s0, s1, s2);
-  }
-  WH_LAUNCH_CHECK("gmm_combine_kernel");
+  WH_LAUNCH(ctx, st, "gmm_stats_kernel", gmm_stats_kernel, dim3((unsigned)M, (unsigned)splits),
+            dim3(64 * kGmmStatsWaves), 0, x, n_rows, ldx, (n_rows - 1) * ldx + d, d, M, gamma, ldg,
+            (n_rows - 1) * ldg + M, mu, part, len_p);
+  const long long total = (long long)M * per;
+  WH_LAUNCH(ctx, st, "gmm_combine_kernel", gmm_combine_kernel, dim3((unsigned)((total + WH_BLOCK - 1) / WH_BLOCK)),
+            dim3(WH_BLOCK), 0, part, len_p, splits, d, M, s0, s1, s2);
   return 0;
 }
 
@@ -434,13 +421,8 @@ extern "C" int wh_gmm_convert(wh_ctx* ctx, void* stream, const double* x, int64_
   const size_t lds = gmm_rows_lds(1, M);
   if (int rc = wh::allow_lds(gmm_rows_kernel<1>, lds)) return rc;
   const long long blocks = (n_rows + kGmmRowTile - 1) / kGmmRowTile;
-  {
-    wh::KernelTimer _kt(ctx, st, "gmm_convert_kernel");
-    hipLaunchKernelGGL(gmm_rows_kernel<1>, dim3((unsigned)blocks), dim3(256), lds, st, x, (long long)n_rows, (long long)ldx,
-                       (n_rows - 1) * ldx + dx, dx, dy, M, mu_x, a, (const double*)nullptr, mu_y, best, g, (long long)ldg,
-                       g ? (n_rows - 1) * ldg + M : 0LL, out, (long long)ldo, (n_rows - 1) * ldo + dy, (double*)nullptr, 0LL,
-                       0LL, (double*)nullptr, (int32_t*)nullptr);
-  }
-  WH_LAUNCH_CHECK("gmm_convert_kernel");
+  WH_LAUNCH(ctx, st, "gmm_convert_kernel", gmm_rows_kernel<1>, dim3((unsigned)blocks), dim3(256), lds, x, n_rows, ldx,
+            (n_rows - 1) * ldx + dx, dx, dy, M, mu_x, a, nullptr, mu_y, best, g, ldg, g ? (n_rows - 1) * ldg + M : 0LL,
+            out, ldo, (n_rows - 1) * ldo + dy, nullptr, 0LL, 0LL, nullptr, nullptr);
   return 0;
 }

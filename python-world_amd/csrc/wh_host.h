@@ -83,6 +83,7 @@ namespace wh {
 int bounds_register(int (*reader)(unsigned long long*));
 void set_error(const std::string& msg);
 int fail(const char* where, hipError_t e);
+inline void clear_runtime_error() { (void)hipGetLastError(); }  // (the runtime's sticky "last error": read is cleared)
 int fail_msg(const char* where, const char* msg);
 int ws_reserve(wh_ctx* ctx, size_t bytes);  // grows ctx->ws (hipFree + hipMalloc => implicit sync)
 inline const double2* twiddle(const wh_ctx* ctx, int n) { return ctx->d_twiddle + n; }
@@ -141,14 +142,15 @@ inline bool dispatch_fft_size(int fft_size, F&& f) {
     default: return false;
   }
 }
-// RAII bracket around one kernel launch: records a start/stop event pair on the launch stream when
-// profiling is enabled (zero cost otherwise).
 // WH_TRACE_LAUNCH=1 (environment, debugging): every launch is announced on stderr and waited for — the last name printed
 // before an abort (a device-side sanitizer finding, a memory fault) is the kernel that caused it.
 inline bool trace_launches() {
   static const bool on = getenv("WH_TRACE_LAUNCH") && getenv("WH_TRACE_LAUNCH")[0] == '1';
   return on;
 }
+namespace detail {
+// RAII bracket around one kernel launch: records a start/stop event pair on the launch stream when the context
+// profiles (zero cost otherwise; no context: an untimed launch, which never leaves a record).
 struct KernelTimer {
   wh_ctx* c;
   hipStream_t st;
@@ -158,7 +160,7 @@ struct KernelTimer {
       fprintf(stderr, "[wh] launch %s\n", name);
       fflush(stderr);
     }
-    if (!c->prof) return;
+    if (!c || !c->prof) return;
     const size_t rec = c->prof_names.size();
     while (c->prof_events.size() < 2 * (rec + 1)) {
       hipEvent_t e;
@@ -174,6 +176,29 @@ struct KernelTimer {
     if (trace_launches()) (void)hipStreamSynchronize(st);
   }
 };
+}  // namespace detail
+// THE way to launch a kernel: bracket it for the profile under `name` (the record name that bench.py, the tools and
+// the tests key on — not necessarily the kernel's symbol), launch it on `st`, read the runtime's error; 0 or
+// wh::fail(name, e).  The kernel comes as a typed pointer: every argument is converted to its parameter's type (no
+// integer casts at the call site), and a run-time choice between instantiations is a choice of pointer in front of ONE
+// launch.
+template <class... P, class... A>
+inline int launch(wh_ctx* ctx, hipStream_t st, const char* name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds,
+                  A&&... args) {
+  static_assert(sizeof...(P) == sizeof...(A), "one argument per kernel parameter");
+  {
+    detail::KernelTimer kt(ctx, st, name);
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
+  }
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(name, e);
+}
+// The same without a profile record (test probes, the flag and batch housekeeping): `name` only prefixes the error.
+template <class... P, class... A>
+inline int launch_untimed(hipStream_t st, const char* name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds,
+                          A&&... args) {
+  return launch(nullptr, st, name, kernel, grid, block, lds, static_cast<A&&>(args)...);
+}
 }  // namespace wh
 
 #define WH_CHECK(expr)                                   \
@@ -186,8 +211,12 @@ struct KernelTimer {
 // thread (a process may hold contexts for several GPUs; allocations and launches follow the current device).
 #define WH_ENTER(ctx) WH_CHECK(hipSetDevice((ctx)->device))
 
-#define WH_LAUNCH_CHECK(name)                            \
-  do {                                                   \
-    hipError_t _e = hipGetLastError();                   \
-    if (_e != hipSuccess) return wh::fail(name, _e);     \
+// A launch as a statement of an entry point that returns the library's status codes.
+#define WH_LAUNCH(...)                                       \
+  do {                                                       \
+    if (int _rc = wh::launch(__VA_ARGS__)) return _rc;       \
+  } while (0)
+#define WH_LAUNCH_UNTIMED(...)                                   \
+  do {                                                           \
+    if (int _rc = wh::launch_untimed(__VA_ARGS__)) return _rc;   \
   } while (0)

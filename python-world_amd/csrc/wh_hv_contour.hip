@@ -633,20 +633,18 @@ int hv_launch_contour(wh_ctx* ctx, hipStream_t st, const HvPlan& p, const HvDev&
   double* d_ch = reinterpret_cast<double*>(d_ws + o_ch);
   if (int rc = persistent_upload(ctx, st, "hv.contour", hc, &d_hc)) return rc;
   const dim3 gf((unsigned)((max_nf1 + 255) / 256), B);
-  { KernelTimer _kt(ctx, st, "hc_base_kernel"); hipLaunchKernelGGL(hc_base_kernel, gf, dim3(256), 0, st, d_meta, d_hc, d_pf0, d_psc, d_lst, d_keep, d_rows); }
-  WH_LAUNCH_CHECK("hc_base_kernel");
-  { KernelTimer _kt(ctx, st, "hc_step1_kernel"); hipLaunchKernelGGL(hc_step1_kernel, gf, dim3(256), 0, st, d_meta, d_hc, d_rows); }
-  WH_LAUNCH_CHECK("hc_step1_kernel");
-  { KernelTimer _kt(ctx, st, "hc_sections_kernel"); hipLaunchKernelGGL(hc_sections_kernel, dim3(B), dim3(256), 0, st, d_meta, d_hc, d_rows, d_runs, d_secs, d_ns); }
-  WH_LAUNCH_CHECK("hc_sections_kernel");
-  { KernelTimer _kt(ctx, st, "hc_extend_kernel"); hipLaunchKernelGGL(hc_extend_kernel, dim3((unsigned)max_secs, B), dim3(64), 0, st, d_meta, d_hc, d_rows, d_pf0, d_lst, d_keep, d_secs, d_ns, d_ch); }
-  WH_LAUNCH_CHECK("hc_extend_kernel");
-  { KernelTimer _kt(ctx, st, "hc_merge_kernel"); hipLaunchKernelGGL(hc_merge_kernel, dim3(B), dim3(256), 0, st, d_meta, d_hc, d_rows, d_pf0, d_psc, d_lst, d_keep, d_secs, d_ns, d_ch, d_runs); }
-  WH_LAUNCH_CHECK("hc_merge_kernel");
-  { KernelTimer _kt(ctx, st, "hc_smooth_kernel"); hipLaunchKernelGGL(hc_smooth_kernel, dim3(B), dim3(256), 0, st, d_meta, d_hc, d_rows, d_runs, d_ch); }
-  WH_LAUNCH_CHECK("hc_smooth_kernel");
-  { KernelTimer _kt(ctx, st, "hc_pick_kernel"); hipLaunchKernelGGL(hc_pick_kernel, dim3((unsigned)((max_nf + 255) / 256), B), dim3(256), 0, st, d_meta, d_hc, d_rows, tp, f0_out, vuv_out); }
-  WH_LAUNCH_CHECK("hc_pick_kernel");
+  WH_LAUNCH(ctx, st, "hc_base_kernel", hc_base_kernel, gf, dim3(256), 0, d_meta, d_hc, d_pf0, d_psc, d_lst, d_keep,
+            d_rows);
+  WH_LAUNCH(ctx, st, "hc_step1_kernel", hc_step1_kernel, gf, dim3(256), 0, d_meta, d_hc, d_rows);
+  WH_LAUNCH(ctx, st, "hc_sections_kernel", hc_sections_kernel, dim3(B), dim3(256), 0, d_meta, d_hc, d_rows, d_runs,
+            d_secs, d_ns);
+  WH_LAUNCH(ctx, st, "hc_extend_kernel", hc_extend_kernel, dim3((unsigned)max_secs, B), dim3(64), 0, d_meta, d_hc,
+            d_rows, d_pf0, d_lst, d_keep, d_secs, d_ns, d_ch);
+  WH_LAUNCH(ctx, st, "hc_merge_kernel", hc_merge_kernel, dim3(B), dim3(256), 0, d_meta, d_hc, d_rows, d_pf0, d_psc,
+            d_lst, d_keep, d_secs, d_ns, d_ch, d_runs);
+  WH_LAUNCH(ctx, st, "hc_smooth_kernel", hc_smooth_kernel, dim3(B), dim3(256), 0, d_meta, d_hc, d_rows, d_runs, d_ch);
+  WH_LAUNCH(ctx, st, "hc_pick_kernel", hc_pick_kernel, dim3((unsigned)((max_nf + 255) / 256), B), dim3(256), 0, d_meta,
+            d_hc, d_rows, tp, f0_out, vuv_out);
   if (dbg_f0_1ms) {
     for (int u = 0; u < B; ++u)
       WH_CHECK(hipMemcpyAsync(dbg_f0_1ms + meta[u].f1_off, d_rows + hc[u].f_base + 4 * meta[u].nf1,

@@ -724,19 +724,17 @@ int hv_launch_decimate(wh_ctx* ctx, hipStream_t st, const HvPlan& p, const doubl
     if (!(rad < 0.9999)) warm = 1 << 30;
     const int chunks = (int)((p.max_len + kHChunk - 1) / kHChunk);
     dim3 gi((chunks + 63) / 64, B);
-    { KernelTimer _kt(ctx, st, "hv_iir_fwd_kernel"); hipLaunchKernelGGL(hv_iir_fwd_kernel, gi, dim3(64), 0, st, x, d.meta, c, warm, d.tmp); }
-    WH_LAUNCH_CHECK("hv_iir_fwd_kernel");
-    { KernelTimer _kt(ctx, st, "hv_iir_bwd_kernel"); hipLaunchKernelGGL(hv_iir_bwd_kernel, gi, dim3(64), 0, st, d.meta, c, warm, p.r, d.tmp, d.y); }
-    WH_LAUNCH_CHECK("hv_iir_bwd_kernel");
+    WH_LAUNCH(ctx, st, "hv_iir_fwd_kernel", hv_iir_fwd_kernel, gi, dim3(64), 0, x, d.meta, c, warm, d.tmp);
+    WH_LAUNCH(ctx, st, "hv_iir_bwd_kernel", hv_iir_bwd_kernel, gi, dim3(64), 0, d.meta, c, warm, p.r, d.tmp, d.y);
   } else {
-    { KernelTimer _kt(ctx, st, "hv_copy_kernel"); hipLaunchKernelGGL(hv_copy_kernel, dim3((unsigned)((p.max_ylen + 255) / 256), B), dim3(256), 0, st, x, d.meta, d.y); }
-    WH_LAUNCH_CHECK("hv_copy_kernel");
+    WH_LAUNCH(ctx, st, "hv_copy_kernel", hv_copy_kernel, dim3((unsigned)((p.max_ylen + 255) / 256), B), dim3(256), 0, x,
+              d.meta, d.y);
   }
-  { KernelTimer _kt(ctx, st, "hv_mean_kernel"); hipLaunchKernelGGL(hv_mean_part_kernel, dim3(kMeanParts, B), dim3(256), 0, st, d.meta, d.y, d.mean + B); }
-  { KernelTimer _kt(ctx, st, "hv_mean_kernel"); hipLaunchKernelGGL(hv_mean_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, d.meta, d.mean + B, B, d.mean); }
-  WH_LAUNCH_CHECK("hv_mean_kernel");
-  { KernelTimer _kt(ctx, st, "hv_pad_kernel"); hipLaunchKernelGGL(hv_pad_kernel, dim3((unsigned)((p.max_ylen + 2 * p.pad + 255) / 256), B), dim3(256), 0, st, d.meta, d.y, d.mean, p.pad, d.z); }
-  WH_LAUNCH_CHECK("hv_pad_kernel");
+  WH_LAUNCH(ctx, st, "hv_mean_kernel", hv_mean_part_kernel, dim3(kMeanParts, B), dim3(256), 0, d.meta, d.y, d.mean + B);
+  WH_LAUNCH(ctx, st, "hv_mean_kernel", hv_mean_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, d.meta, d.mean + B,
+            B, d.mean);
+  WH_LAUNCH(ctx, st, "hv_pad_kernel", hv_pad_kernel, dim3((unsigned)((p.max_ylen + 2 * p.pad + 255) / 256), B),
+            dim3(256), 0, d.meta, d.y, d.mean, p.pad, d.z);
   return 0;
 }
 
@@ -759,19 +757,21 @@ int hv_launch_raw_detect(wh_ctx* ctx, hipStream_t st, const HvPlan& p, double f0
   const int B = p.B, n_bands = p.n_bands;
   if (p.use_rawdet) {
     const int rd_xcd = B >= 8 ? 8 : 1;
-    { KernelTimer _kt(ctx, st, "hv_rawdet_kernel"); hipLaunchKernelGGL(hv_rawdet_kernel, dim3((unsigned)((int64_t)((B + rd_xcd - 1) / rd_xcd) * rd_xcd * p.max_ntile)), dim3(kRawTile), 0, st, d.meta, d.jobs, d.band_f0, d.hint, n_bands, B, rd_xcd, (int)p.max_ntile, p.fs_d, f0_floor, f0_ceil, d.dc, d.dn, dbg_raw ? d.raw : nullptr); }
-    WH_LAUNCH_CHECK("hv_rawdet_kernel");
+    WH_LAUNCH(ctx, st, "hv_rawdet_kernel", hv_rawdet_kernel,
+              dim3((unsigned)((int64_t)((B + rd_xcd - 1) / rd_xcd) * rd_xcd * p.max_ntile)), dim3(kRawTile), 0, d.meta,
+              d.jobs, d.band_f0, d.hint, n_bands, B, rd_xcd, (int)p.max_ntile, p.fs_d, f0_floor, f0_ceil, d.dc, d.dn,
+              dbg_raw ? d.raw : nullptr);
     if (dbg_raw) WH_CHECK(hipMemcpyAsync(dbg_raw, d.raw, sizeof(double) * p.f1_tot * n_bands, hipMemcpyDeviceToDevice, st));
     return 0;
   }
   // frames of an (utterance, channel) cut into segments with a workgroup each while the grid is a few rounds of the chip
   // (2560 workgroups at ten per CU): 1.80 -> 1.70 ms at 64 utterances; large batches keep one (no second cursor search)
   const int raw_segs = (int64_t)n_bands * B < 16 * 2560 ? 4 : 1;
-  { KernelTimer _kt(ctx, st, "hv_raw_kernel"); hipLaunchKernelGGL(hv_raw_kernel, dim3(n_bands, B, raw_segs), dim3(kRawTile), 0, st, d.meta, d.jobs, d.band_f0, n_bands, p.fs_d, f0_floor, f0_ceil, d.raw, d.live, dbg_raw ? 1 : 0); }
-  WH_LAUNCH_CHECK("hv_raw_kernel");
+  WH_LAUNCH(ctx, st, "hv_raw_kernel", hv_raw_kernel, dim3(n_bands, B, raw_segs), dim3(kRawTile), 0, d.meta, d.jobs,
+            d.band_f0, n_bands, p.fs_d, f0_floor, f0_ceil, d.raw, d.live, dbg_raw ? 1 : 0);
   if (dbg_raw) WH_CHECK(hipMemcpyAsync(dbg_raw, d.raw, sizeof(double) * p.f1_tot * n_bands, hipMemcpyDeviceToDevice, st));
-  { KernelTimer _kt(ctx, st, "hv_detect_kernel"); hipLaunchKernelGGL(hv_detect_kernel, dim3((unsigned)((p.max_nf1 + 255) / 256), B), dim3(256), 0, st, d.meta, n_bands, d.raw, d.live, d.dc, d.dn); }
-  WH_LAUNCH_CHECK("hv_detect_kernel");
+  WH_LAUNCH(ctx, st, "hv_detect_kernel", hv_detect_kernel, dim3((unsigned)((p.max_nf1 + 255) / 256), B), dim3(256), 0,
+            d.meta, n_bands, d.raw, d.live, d.dc, d.dn);
   return 0;
 }
 

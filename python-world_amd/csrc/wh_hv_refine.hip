@@ -851,9 +851,9 @@ int launch_refine_form(wh_ctx* ctx, hipStream_t st, const HvPlan& p, double f0_f
   int item_cap = refine_item_cap(WTAB);
   if (cap_env >= kRows && cap_env < item_cap) item_cap = cap_env;
   if (int rc = allow_lds(&hv_refine_kernel<TWL, WTAB>, lds)) return rc;
-  KernelTimer _kt(ctx, st, "hv_refine_kernel");
-  hipLaunchKernelGGL((hv_refine_kernel<TWL, WTAB>), grid, dim3(256), lds, st, d.meta, d.y, d.dc, d.dn, p.fs_d, f0_floor, f0_ceil,
-                     p.hmax, seglen, ctx->d_twiddle, tw_n, d_rot, d_wtab, d.rf0, d.rsc, d.lst, item_cap);
+  WH_LAUNCH(ctx, st, "hv_refine_kernel", hv_refine_kernel<TWL, WTAB>, grid, dim3(256), lds, d.meta, d.y, d.dc, d.dn,
+            p.fs_d, f0_floor, f0_ceil, p.hmax, seglen, ctx->d_twiddle, tw_n, d_rot, d_wtab, d.rf0, d.rsc, d.lst,
+            item_cap);
   return 0;
 }
 
@@ -871,17 +871,15 @@ int hv_launch_refine(wh_ctx* ctx, hipStream_t st, const HvPlan& p, double f0_flo
   if (tw_n) {
     const double2* d_wtab = nullptr;
     if (int rc = window_table(ctx, p.fs_d, p.hmax, &d_wtab)) return rc;
-    if (int rc = launch_refine_form<true, true>(ctx, st, p, f0_floor, f0_ceil, d, tw_n, d_rot, d_wtab)) return rc;
-  } else if (int rc = launch_refine_form<false, false>(ctx, st, p, f0_floor, f0_ceil, d, 0, d_rot, nullptr)) {
-    return rc;
+    return launch_refine_form<true, true>(ctx, st, p, f0_floor, f0_ceil, d, tw_n, d_rot, d_wtab);
   }
-  WH_LAUNCH_CHECK("hv_refine_kernel");
-  return 0;
+  return launch_refine_form<false, false>(ctx, st, p, f0_floor, f0_ceil, d, 0, d_rot, nullptr);
 }
 
 int hv_launch_prune(wh_ctx* ctx, hipStream_t st, const HvPlan& p, const HvDev& d) {
-  { KernelTimer _kt(ctx, st, "hv_prune_kernel"); hipLaunchKernelGGL(hv_prune_kernel, dim3((unsigned)((p.max_nf1 + kPruneFrames - 1) / kPruneFrames), p.B), dim3(256), 0, st, d.meta, d.rf0, d.lst, d.keep); }
-  WH_LAUNCH_CHECK("hv_prune_kernel");
+  WH_LAUNCH(ctx, st, "hv_prune_kernel", hv_prune_kernel,
+            dim3((unsigned)((p.max_nf1 + kPruneFrames - 1) / kPruneFrames), p.B), dim3(256), 0, d.meta, d.rf0, d.lst,
+            d.keep);
   return 0;
 }
 

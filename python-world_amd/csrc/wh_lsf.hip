@@ -251,12 +251,8 @@ extern "C" int wh_lpc_levinson(wh_ctx* ctx, void* stream, const double* r, int64
   const size_t lds = (size_t)2 * (p + 1) * WH_WAVE * sizeof(double);
   if (int rc = wh::allow_lds(lpc_levinson_kernel, lds)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  {
-    wh::KernelTimer _kt(ctx, st, "lpc_levinson_kernel");
-    hipLaunchKernelGGL(lpc_levinson_kernel, dim3((unsigned)blocks), dim3(WH_WAVE), lds, st, r, (long long)n_frames,
-                       (long long)ldr, p, a, (long long)lda, e, refl, (long long)ldk, ctx->d_flags);
-  }
-  WH_LAUNCH_CHECK("lpc_levinson_kernel");
+  WH_LAUNCH(ctx, st, "lpc_levinson_kernel", lpc_levinson_kernel, dim3((unsigned)blocks), dim3(WH_WAVE), lds, r,
+            n_frames, ldr, p, a, lda, e, refl, ldk, ctx->d_flags);
   return 0;
 }
 
@@ -278,18 +274,9 @@ extern "C" int wh_lsf_from_lpc(wh_ctx* ctx, void* stream, const double* a, int64
   hipStream_t st = (hipStream_t)stream;
   void* d_grid = nullptr;
   if (int rc = wh::persistent_upload(ctx, st, "lsf.grid", h_grid, (size_t)n_grid * sizeof(double), &d_grid)) return rc;
-  {
-    wh::KernelTimer _kt(ctx, st, "lsf_from_lpc_kernel");
-    if (p <= 32)
-      hipLaunchKernelGGL(lsf_from_lpc_kernel<32>, dim3((unsigned)blocks), dim3(kLsfWaves * WH_WAVE), 0, st, a,
-                         (long long)n_frames, (long long)lda, p, reinterpret_cast<const double*>(d_grid), x,
-                         (long long)ldx, level_out, ctx->d_flags);
-    else
-      hipLaunchKernelGGL(lsf_from_lpc_kernel<64>, dim3((unsigned)blocks), dim3(kLsfWaves * WH_WAVE), 0, st, a,
-                         (long long)n_frames, (long long)lda, p, reinterpret_cast<const double*>(d_grid), x,
-                         (long long)ldx, level_out, ctx->d_flags);
-  }
-  WH_LAUNCH_CHECK("lsf_from_lpc_kernel");
+  WH_LAUNCH(ctx, st, "lsf_from_lpc_kernel", p <= 32 ? lsf_from_lpc_kernel<32> : lsf_from_lpc_kernel<64>,
+            dim3((unsigned)blocks), dim3(kLsfWaves * WH_WAVE), 0, a, n_frames, lda, p,
+            reinterpret_cast<const double*>(d_grid), x, ldx, level_out, ctx->d_flags);
   return 0;
 }
 
@@ -310,11 +297,7 @@ extern "C" int wh_lsf_envelope(wh_ctx* ctx, void* stream, const double* rows, in
   hipStream_t st = (hipStream_t)stream;
   void* d_cos = nullptr;
   if (int rc = wh::persistent_upload(ctx, st, "lsf.bins", h_cos, (size_t)k_bins * sizeof(double), &d_cos)) return rc;
-  {
-    wh::KernelTimer _kt(ctx, st, "lsf_envelope_kernel");
-    hipLaunchKernelGGL(lsf_envelope_kernel, dim3((unsigned)blocks), dim3(kEnvThreads), 0, st, rows, (long long)n_frames,
-                       (long long)ldr, p, reinterpret_cast<const double*>(d_cos), k_bins, out, (long long)ldo);
-  }
-  WH_LAUNCH_CHECK("lsf_envelope_kernel");
+  WH_LAUNCH(ctx, st, "lsf_envelope_kernel", lsf_envelope_kernel, dim3((unsigned)blocks), dim3(kEnvThreads), 0, rows,
+            n_frames, ldr, p, reinterpret_cast<const double*>(d_cos), k_bins, out, ldo);
   return 0;
 }

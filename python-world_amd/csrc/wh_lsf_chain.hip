@@ -185,12 +185,8 @@ extern "C" int wh_lsf_repair(wh_ctx* ctx, void* stream, const double* w, int64_t
   if (blocks > 0x7fffffffLL) return wh::fail_msg("wh_lsf_repair", "too many frames for one call");
   const size_t lds = (size_t)p * kRepairPitch * sizeof(double);
   hipStream_t st = (hipStream_t)stream;
-  {
-    wh::KernelTimer _kt(ctx, st, "lsf_repair_kernel");
-    hipLaunchKernelGGL(lsf_repair_kernel, dim3((unsigned)blocks), dim3(WH_WAVE), lds, st, w, (long long)n_frames,
-                       (long long)ldw, p, gap, hi, out, (long long)ldo, changed);
-  }
-  WH_LAUNCH_CHECK("lsf_repair_kernel");
+  WH_LAUNCH(ctx, st, "lsf_repair_kernel", lsf_repair_kernel, dim3((unsigned)blocks), dim3(WH_WAVE), lds, w, n_frames,
+            ldw, p, gap, hi, out, ldo, changed);
   return 0;
 }
 
@@ -212,13 +208,8 @@ extern "C" int wh_lsf_distortion(wh_ctx* ctx, void* stream, const double* rows_a
   hipStream_t st = (hipStream_t)stream;
   void* d_cos = nullptr;
   if (int rc = wh::persistent_upload(ctx, st, "lsf.bins", h_cos, (size_t)k_bins * sizeof(double), &d_cos)) return rc;
-  {
-    wh::KernelTimer _kt(ctx, st, "lsf_distortion_kernel");
-    hipLaunchKernelGGL(lsf_distortion_kernel, dim3((unsigned)blocks), dim3(kDistWaves * WH_WAVE), 0, st, rows_a,
-                       (long long)n_rows_a, (long long)lda, rows_b, (long long)n_rows_b, (long long)ldb, p,
-                       reinterpret_cast<const long long*>(idx_a), reinterpret_cast<const long long*>(idx_b),
-                       (long long)n_pairs, reinterpret_cast<const double*>(d_cos), k_bins, out);
-  }
-  WH_LAUNCH_CHECK("lsf_distortion_kernel");
+  WH_LAUNCH(ctx, st, "lsf_distortion_kernel", lsf_distortion_kernel, dim3((unsigned)blocks), dim3(kDistWaves * WH_WAVE),
+            0, rows_a, n_rows_a, lda, rows_b, n_rows_b, ldb, p, reinterpret_cast<const long long*>(idx_a),
+            reinterpret_cast<const long long*>(idx_b), n_pairs, reinterpret_cast<const double*>(d_cos), k_bins, out);
   return 0;
 }

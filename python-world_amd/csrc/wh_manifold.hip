@@ -317,13 +317,8 @@ extern "C" int wh_dense_stack(wh_ctx* ctx, void* stream, const double* x, int64_
   const long long x_n = (n_rows - 1) * ldx + d;
   const long long tap_n = tap_layer >= 0 ? (n_rows - 1) * ld_tap + h_units[tap_layer] : 0;
   const long long out_n = (n_rows - 1) * ldo + n_out;
-  {
-    wh::KernelTimer _kt(ctx, st, "dense_stack_kernel");
-    hipLaunchKernelGGL(dense_stack_kernel, dim3((unsigned)wh::xcd_grid(n_tiles)), dim3(256), 0, st, x, x_n,
-                       (long long)n_rows, d, (long long)ldx, d_in, d_seg, n_seg, window, d_is, d_plan, n_layers, tap_layer,
-                       tap_f32 ? 1 : 0, d_w, w_total, d_b, b_total, tap_layer >= 0 ? tap_out : nullptr, tap_n, (long long)ld_tap, d_os, out, out_n,
-                       (long long)ldo);
-  }
-  WH_LAUNCH_CHECK("dense_stack_kernel");
+  WH_LAUNCH(ctx, st, "dense_stack_kernel", dense_stack_kernel, dim3((unsigned)wh::xcd_grid(n_tiles)), dim3(256), 0, x,
+            x_n, n_rows, d, ldx, d_in, d_seg, n_seg, window, d_is, d_plan, n_layers, tap_layer, tap_f32 ? 1 : 0, d_w,
+            w_total, d_b, b_total, tap_layer >= 0 ? tap_out : nullptr, tap_n, ld_tap, d_os, out, out_n, ldo);
   return 0;
 }

@@ -257,13 +257,9 @@ extern "C" int wh_delta_features(wh_ctx* ctx, void* stream, const wh_batch* b, c
   const long long blocks = (total + WH_BLOCK - 1) / WH_BLOCK;
   if (blocks > 0x7fffffffLL) return wh::fail_msg("wh_delta_features", "too many output elements for one call");
   hipStream_t st = (hipStream_t)stream;
-  {
-    wh::KernelTimer _kt(ctx, st, "delta_features_kernel");
-    hipLaunchKernelGGL(delta_features_kernel, dim3((unsigned)blocks), dim3(WH_BLOCK), 0, st, b->d_frame_off, b->n_utt,
-                       b->d_frame_utt, frames, x, (long long)ldx, (frames - 1) * ldx + d, d, n_win, half, win, out,
-                       (long long)ldo, (frames - 1) * ldo + width);
-  }
-  WH_LAUNCH_CHECK("delta_features_kernel");
+  WH_LAUNCH(ctx, st, "delta_features_kernel", delta_features_kernel, dim3((unsigned)blocks), dim3(WH_BLOCK), 0,
+            b->d_frame_off, b->n_utt, b->d_frame_utt, frames, x, ldx, (frames - 1) * ldx + d, d, n_win, half, win, out,
+            ldo, (frames - 1) * ldo + width);
   return 0;
 }
 
@@ -295,17 +291,8 @@ extern "C" int wh_mlpg(wh_ctx* ctx, void* stream, const wh_batch* b, const doubl
   double* mult = reinterpret_cast<double*>(scratch);
   const long long len_m = (frames - 1) * ldm + width, len_v = ldv ? (frames - 1) * ldv + width : width;
   const long long len_o = (frames - 1) * ldo + d;
-  {
-    wh::KernelTimer _kt(ctx, st, "mlpg_kernel");
-#define WH_MLPG_LAUNCH(BB)                                                                                               \
-  hipLaunchKernelGGL(mlpg_kernel<BB>, dim3((unsigned)waves), dim3(WH_WAVE), 0, st, b->d_frame_off, b->n_utt, frames, mean, \
-                     (long long)ldm, len_m, var, (long long)ldv, len_v, d, n_win, win, out, (long long)ldo, len_o, mult,  \
-                     len_l, pivots_out, ctx->d_flags)
-    if (B == 0) WH_MLPG_LAUNCH(0);
-    else if (B == 2) WH_MLPG_LAUNCH(2);
-    else WH_MLPG_LAUNCH(4);
-#undef WH_MLPG_LAUNCH
-  }
-  WH_LAUNCH_CHECK("mlpg_kernel");
+  WH_LAUNCH(ctx, st, "mlpg_kernel", B == 0 ? mlpg_kernel<0> : B == 2 ? mlpg_kernel<2> : mlpg_kernel<4>,
+            dim3((unsigned)waves), dim3(WH_WAVE), 0, b->d_frame_off, b->n_utt, frames, mean, ldm, len_m, var, ldv,
+            len_v, d, n_win, win, out, ldo, len_o, mult, len_l, pivots_out, ctx->d_flags);
   return 0;
 }

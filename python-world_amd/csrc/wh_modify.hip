@@ -100,8 +100,8 @@ extern "C" int wh_warp_spectrum(wh_ctx* ctx, void* stream, double* spectrogram, 
   if (int rc = wh::persistent_upload(ctx, st, "warp.den", den, &d_den)) return rc;
   const size_t lds = sizeof(double) * (size_t)k_bins;
   if (int rc = wh::allow_lds(&warp_spectrum_kernel, lds)) return rc;
-  { wh::KernelTimer _kt(ctx, st, "warp_spectrum_kernel"); hipLaunchKernelGGL(warp_spectrum_kernel, dim3((unsigned)n_frames), dim3(256), lds, st, spectrogram, (long long)n_frames, k_bins, d_src, d_dx, d_den); }
-  WH_LAUNCH_CHECK("warp_spectrum_kernel");
+  WH_LAUNCH(ctx, st, "warp_spectrum_kernel", warp_spectrum_kernel, dim3((unsigned)n_frames), dim3(256), lds,
+            spectrogram, n_frames, k_bins, d_src, d_dx, d_den);
   return 0;
 }
 
@@ -116,8 +116,8 @@ extern "C" int wh_modify_duration(wh_ctx* ctx, void* stream, const wh_batch* b, 
   double *d_xp = nullptr, *d_fp = nullptr;
   if (int rc = wh::persistent_upload(ctx, st, "moddur.xp", xp, &d_xp)) return rc;
   if (int rc = wh::persistent_upload(ctx, st, "moddur.fp", fp, &d_fp)) return rc;
-  { wh::KernelTimer _kt(ctx, st, "modify_duration_kernel"); hipLaunchKernelGGL(modify_duration_kernel, dim3((unsigned)((b->total_frames + 255) / 256)), dim3(256), 0, st, tp_in, tp_out, b->d_frame_off, b->d_frame_utt, (long long)b->total_frames, d_xp, d_fp, n_anchor); }
-  WH_LAUNCH_CHECK("modify_duration_kernel");
+  WH_LAUNCH(ctx, st, "modify_duration_kernel", modify_duration_kernel, dim3((unsigned)((b->total_frames + 255) / 256)),
+            dim3(256), 0, tp_in, tp_out, b->d_frame_off, b->d_frame_utt, b->total_frames, d_xp, d_fp, n_anchor);
   return 0;
 }
 
@@ -126,8 +126,8 @@ extern "C" int wh_pcm16_to_f64(wh_ctx* ctx, void* stream, const int16_t* pcm, in
   WH_ENTER(ctx);
   if (n <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  { wh::KernelTimer _kt(ctx, st, "pcm16_to_f64_kernel"); hipLaunchKernelGGL(pcm16_to_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pcm, (long long)n, x); }
-  WH_LAUNCH_CHECK("pcm16_to_f64_kernel");
+  WH_LAUNCH(ctx, st, "pcm16_to_f64_kernel", pcm16_to_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, pcm,
+            n, x);
   return 0;
 }
 
@@ -136,7 +136,7 @@ extern "C" int wh_f64_to_pcm16(wh_ctx* ctx, void* stream, const double* y, int64
   WH_ENTER(ctx);
   if (n <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  { wh::KernelTimer _kt(ctx, st, "f64_to_pcm16_kernel"); hipLaunchKernelGGL(f64_to_pcm16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, y, (long long)n, pcm); }
-  WH_LAUNCH_CHECK("f64_to_pcm16_kernel");
+  WH_LAUNCH(ctx, st, "f64_to_pcm16_kernel", f64_to_pcm16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, y, n,
+            pcm);
   return 0;
 }

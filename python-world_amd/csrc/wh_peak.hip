@@ -49,9 +49,7 @@ extern "C" int wh_peak_normalise(wh_ctx* ctx, void* stream, double* y, const int
   unsigned long long* d_peak = reinterpret_cast<unsigned long long*>(ctx->ws);
   WH_CHECK(hipMemsetAsync(d_peak, 0, sizeof(unsigned long long) * (size_t)n_utt, st));
   const unsigned gx = (unsigned)std::min<int64_t>(64, (max_n + 4 * 256 - 1) / (4 * 256) + 1);
-  { wh::KernelTimer _kt(ctx, st, "peak_max_kernel"); hipLaunchKernelGGL(peak_max_kernel, dim3(gx, n_utt), dim3(256), 0, st, y, d_off, d_peak); }
-  WH_LAUNCH_CHECK("peak_max_kernel");
-  { wh::KernelTimer _kt(ctx, st, "peak_scale_kernel"); hipLaunchKernelGGL(peak_scale_kernel, dim3(gx, n_utt), dim3(256), 0, st, y, d_off, d_peak); }
-  WH_LAUNCH_CHECK("peak_scale_kernel");
+  WH_LAUNCH(ctx, st, "peak_max_kernel", peak_max_kernel, dim3(gx, n_utt), dim3(256), 0, y, d_off, d_peak);
+  WH_LAUNCH(ctx, st, "peak_scale_kernel", peak_scale_kernel, dim3(gx, n_utt), dim3(256), 0, y, d_off, d_peak);
   return 0;
 }

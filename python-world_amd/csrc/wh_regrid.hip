@@ -283,8 +283,9 @@ extern "C" int wh_interp_contour(wh_ctx* ctx, void* stream, const wh_batch* b, c
   if (int rc = wh::persistent_upload(ctx, st, "contour.value", kv, &d_kv)) return rc;
   const long long blocks = (b->total_frames + 255) / 256;
   if (blocks > 0x7fffffffLL) return wh::fail_msg("wh_interp_contour", "too many frames for one launch");
-  { wh::KernelTimer _kt(ctx, st, "interp_contour_kernel"); hipLaunchKernelGGL(interp_contour_kernel, dim3((unsigned)blocks), dim3(256), 0, st, tp, b->d_frame_utt, (long long)b->total_frames, d_off, b->n_utt, d_kt, d_kv, (long long)n_knots, voiced_rule, out, voiced_rule ? vuv_out : nullptr); }
-  WH_LAUNCH_CHECK("interp_contour_kernel");
+  WH_LAUNCH(ctx, st, "interp_contour_kernel", interp_contour_kernel, dim3((unsigned)blocks), dim3(256), 0, tp,
+            b->d_frame_utt, b->total_frames, d_off, b->n_utt, d_kt, d_kv, n_knots, voiced_rule, out,
+            voiced_rule ? vuv_out : nullptr);
   return 0;
 }
 
@@ -316,18 +317,11 @@ extern "C" int wh_regrid_rows(wh_ctx* ctx, void* stream, const wh_batch* src, co
   const int rows = regrid_rows_per_group(k_bins);
   const long long groups = (n_dst + rows - 1) / rows;
   if (pblocks > 0x7fffffffLL || groups > 0x7fffffffLL) return wh::fail_msg("wh_regrid_rows", "too many frames for one launch");
-  { wh::KernelTimer _kt(ctx, st, "regrid_plan_kernel"); hipLaunchKernelGGL(regrid_plan_kernel, dim3((unsigned)pblocks), dim3(256), 0, st, tp_src, tp_dst, src->d_frame_off, dst->d_frame_utt, dst->n_utt, n_src, n_dst, pj, pdx, pden, pdx2); }
-  WH_LAUNCH_CHECK("regrid_plan_kernel");
+  WH_LAUNCH(ctx, st, "regrid_plan_kernel", regrid_plan_kernel, dim3((unsigned)pblocks), dim3(256), 0, tp_src, tp_dst,
+            src->d_frame_off, dst->d_frame_utt, dst->n_utt, n_src, n_dst, pj, pdx, pden, pdx2);
   const bool vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-  {
-    wh::KernelTimer _kt(ctx, st, "regrid_rows_kernel");
-    if (vec)
-      hipLaunchKernelGGL(regrid_rows_kernel<true>, dim3((unsigned)groups), dim3(kRgThreads), 0, st, in, out, pj, pdx, pden,
-                         pdx2, n_src, n_dst, k_bins, rows, positive_rule);
-    else
-      hipLaunchKernelGGL(regrid_rows_kernel<false>, dim3((unsigned)groups), dim3(kRgThreads), 0, st, in, out, pj, pdx, pden,
-                         pdx2, n_src, n_dst, k_bins, rows, positive_rule);
-  }
-  WH_LAUNCH_CHECK("regrid_rows_kernel");
+  WH_LAUNCH(ctx, st, "regrid_rows_kernel", vec ? regrid_rows_kernel<true> : regrid_rows_kernel<false>,
+            dim3((unsigned)groups), dim3(kRgThreads), 0, in, out, pj, pdx, pden, pdx2, n_src, n_dst, k_bins, rows,
+            positive_rule);
   return 0;
 }

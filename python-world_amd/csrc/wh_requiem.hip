@@ -301,8 +301,8 @@ int launch_req_filter(wh_ctx* ctx, hipStream_t st, int B, int64_t max_nf, int64_
     if (it == ctx->tables.end()) {
       double* d = nullptr;
       WH_CHECK(hipMalloc((void**)&d, sizeof(double) * (size_t)wlen));
-      hipLaunchKernelGGL(req_hann_kernel, dim3((unsigned)((wlen + 255) / 256)), dim3(256), 0, st, d, wlen);
-      WH_LAUNCH_CHECK("req_hann_kernel");
+      WH_LAUNCH_UNTIMED(st, "req_hann_kernel", req_hann_kernel, dim3((unsigned)((wlen + 255) / 256)), dim3(256), 0, d,
+                        wlen);
       ctx->tables[key] = d;
       ctx->table_bytes += sizeof(double) * (size_t)wlen;
       d_hann = d;
@@ -311,24 +311,16 @@ int launch_req_filter(wh_ctx* ctx, hipStream_t st, int B, int64_t max_nf, int64_
     }
   }
   const size_t lds = sizeof(double2) * 2 * (N / 2 + 1) + 64;  // the chain's buffer and the excitation frame's
+  const bool run = runs && RUNF > 1;
   if (max_nf >= 4) {
-    wh::KernelTimer _kt(ctx, st, "req_filter_kernel");
-    if (runs && RUNF > 1) {
-      const size_t lds_run = lds + sizeof(double) * (size_t)((RUNF - 1) * max_hop + N);  // + the run's sums
-      if (int rc = wh::allow_lds(&req_filter_kernel<N, RUNF>, lds_run)) return rc;
-      hipLaunchKernelGGL((req_filter_kernel<N, RUNF>), dim3((unsigned)((max_nf - 3 + RUNF - 1) / RUNF), B), dim3(ft_syn(N)), lds_run, st, d_meta, d_rq, spec, exc, ctx->d_twiddle, rows, d_hann);
-    } else {
-      if (int rc = wh::allow_lds(&req_filter_kernel<N, 1>, lds)) return rc;
-      hipLaunchKernelGGL((req_filter_kernel<N, 1>), dim3((unsigned)(max_nf - 3), B), dim3(ft_syn(N)), lds, st, d_meta, d_rq, spec, exc, ctx->d_twiddle, rows, d_hann);
-    }
+    const size_t lds_k = run ? lds + sizeof(double) * (size_t)((RUNF - 1) * max_hop + N) : lds;  // + the run's sums
+    const auto k = run ? req_filter_kernel<N, RUNF> : req_filter_kernel<N, 1>;
+    if (int rc = wh::allow_lds(k, lds_k)) return rc;
+    WH_LAUNCH(ctx, st, "req_filter_kernel", k, dim3((unsigned)(run ? (max_nf - 3 + RUNF - 1) / RUNF : max_nf - 3), B),
+              dim3(ft_syn(N)), lds_k, d_meta, d_rq, spec, exc, ctx->d_twiddle, rows, d_hann);
   }
-  WH_LAUNCH_CHECK("req_filter_kernel");
-  {
-    wh::KernelTimer _kt(ctx, st, "req_gather_kernel");
-    if (runs && RUNF > 1) hipLaunchKernelGGL((req_gather_kernel<N, RUNF>), dim3((unsigned)((max_ny + 255) / 256), B), dim3(256), 0, st, d_meta, d_rq, rows, y);
-    else hipLaunchKernelGGL((req_gather_kernel<N, 1>), dim3((unsigned)((max_ny + 255) / 256), B), dim3(256), 0, st, d_meta, d_rq, rows, y);
-  }
-  WH_LAUNCH_CHECK("req_gather_kernel");
+  WH_LAUNCH(ctx, st, "req_gather_kernel", run ? req_gather_kernel<N, RUNF> : req_gather_kernel<N, 1>,
+            dim3((unsigned)((max_ny + 255) / 256), B), dim3(256), 0, d_meta, d_rq, rows, y);
   return 0;
 }
 
@@ -399,12 +391,13 @@ extern "C" int wh_synthesis_requiem(wh_ctx* ctx, void* stream, const wh_batch* b
   if (int rc = wh::persistent_upload(ctx, st, "syn.req", rq, &d_rq)) return rc;
   double* d_rows = reinterpret_cast<double*>(ws + o_rows);
   if (int rc = wh::launch_pulses(ctx, st, B, max_ny, d_meta, tp, f0, vuv, fs, 0.0, h_y_off, ws, lay)) return rc;
-  { wh::KernelTimer _kt(ctx, st, "req_linap_kernel"); hipLaunchKernelGGL(req_linap_kernel, dim3((unsigned)((F * n_bands + 255) / 256)), dim3(256), 0, st, band_aperiodicity, F * n_bands, d_lin); }
-  WH_LAUNCH_CHECK("req_linap_kernel");
-  { wh::KernelTimer _kt(ctx, st, "req_pulse_weights_kernel"); hipLaunchKernelGGL(req_pulse_weights_kernel, dim3((unsigned)((pulse_cap + 255) / 256), B), dim3(256), 0, st, d_meta, tp, d_lin, n_bands, d_pi, d_pc, d_vuv, d_pt, d_pw); }
-  WH_LAUNCH_CHECK("req_pulse_weights_kernel");
-  { wh::KernelTimer _kt(ctx, st, "req_excite_kernel"); hipLaunchKernelGGL(req_excite_kernel, dim3((unsigned)((max_ny + 255) / 256), B), dim3(256), 0, st, d_meta, d_rq, tp, d_lin, n_bands, noise_seed, noise_len, pulse_seed, pulse_fft, d_pi, d_pc, d_pt, d_pw, d_exc); }
-  WH_LAUNCH_CHECK("req_excite_kernel");
+  WH_LAUNCH(ctx, st, "req_linap_kernel", req_linap_kernel, dim3((unsigned)((F * n_bands + 255) / 256)), dim3(256), 0,
+            band_aperiodicity, F * n_bands, d_lin);
+  WH_LAUNCH(ctx, st, "req_pulse_weights_kernel", req_pulse_weights_kernel, dim3((unsigned)((pulse_cap + 255) / 256), B),
+            dim3(256), 0, d_meta, tp, d_lin, n_bands, d_pi, d_pc, d_vuv, d_pt, d_pw);
+  WH_LAUNCH(ctx, st, "req_excite_kernel", req_excite_kernel, dim3((unsigned)((max_ny + 255) / 256), B), dim3(256), 0,
+            d_meta, d_rq, tp, d_lin, n_bands, noise_seed, noise_len, pulse_seed, pulse_fft, d_pi, d_pc, d_pt, d_pw,
+            d_exc);
   int rc = 0;
   wh::dispatch_fft_size(fft_size, [&](auto n) {
     rc = launch_req_filter<decltype(n)::value>(ctx, st, B, max_nf, max_ny, max_hop, runs, d_meta, d_rq, spectrogram, d_exc, d_rows, y, uniform_hop);

@@ -320,23 +320,17 @@ extern "C" int wh_resample_poly(wh_ctx* ctx, void* stream, int n_utt, const int6
                                          "resample.tilesL1"};
   static const char* names[kVariants] = {"resample_kernel<24>", "resample_kernel<32>", "resample_kernel<48>",
                                          "resample_kernel<64>", "resample_kernel<0>"};
+  static decltype(&resample_kernel<0>) const kernels[kVariants] = {resample_kernel<24>, resample_kernel<32>,
+                                                                   resample_kernel<48>, resample_kernel<64>,
+                                                                   resample_kernel<0>};
   const size_t lds = sizeof(double) * kRsLds;
   for (int v = 0; v < kVariants; ++v) {
     if (tl[v].empty()) continue;
     RsTile* d_tiles = nullptr;
     if (int rc = wh::persistent_upload(ctx, st, slots[v], tl[v], &d_tiles)) return rc;
     const long long n = (long long)tl[v].size();
-    const dim3 grid((unsigned)wh::xcd_grid(n));
-    wh::KernelTimer _kt(ctx, st, names[v]);
-    const long long tn = tab_n;
-    switch (pmax[v]) {
-      case 24: hipLaunchKernelGGL(resample_kernel<24>, grid, dim3(kRsThreads), lds, st, x, x_n, y, y_n, d_utt, n_utt, d_tiles, n, d_tab, tn); break;
-      case 32: hipLaunchKernelGGL(resample_kernel<32>, grid, dim3(kRsThreads), lds, st, x, x_n, y, y_n, d_utt, n_utt, d_tiles, n, d_tab, tn); break;
-      case 48: hipLaunchKernelGGL(resample_kernel<48>, grid, dim3(kRsThreads), lds, st, x, x_n, y, y_n, d_utt, n_utt, d_tiles, n, d_tab, tn); break;
-      case 64: hipLaunchKernelGGL(resample_kernel<64>, grid, dim3(kRsThreads), lds, st, x, x_n, y, y_n, d_utt, n_utt, d_tiles, n, d_tab, tn); break;
-      default: hipLaunchKernelGGL(resample_kernel<0>, grid, dim3(kRsThreads), lds, st, x, x_n, y, y_n, d_utt, n_utt, d_tiles, n, d_tab, tn);
-    }
-    WH_LAUNCH_CHECK(names[v]);
+    WH_LAUNCH(ctx, st, names[v], kernels[v], dim3((unsigned)wh::xcd_grid(n)), dim3(kRsThreads), lds, x, x_n, y, y_n,
+              d_utt, n_utt, d_tiles, n, d_tab, tab_n);
   }
   return 0;
 }

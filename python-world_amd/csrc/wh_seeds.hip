@@ -176,17 +176,17 @@ extern "C" int wh_requiem_seeds(wh_ctx* ctx, void* stream, double fs, int fft_si
   int32_t* d_sl = reinterpret_cast<int32_t*>(ws + o_sl);
   int32_t* d_ns = reinterpret_cast<int32_t*>(ws + o_ns);
   WH_CHECK(hipMemsetAsync(d_vel, 0, sizeof(double) * n, st));
-  { wh::KernelTimer _kt(ctx, st, "velvet_layout_kernel"); hipLaunchKernelGGL(velvet_layout_kernel, dim3(1), dim3(64), 0, st, n, lens[0], lens[1], lens[2], seed, max_seg, d_ss, d_sl, d_ns); }
-  WH_LAUNCH_CHECK("velvet_layout_kernel");
-  { wh::KernelTimer _kt(ctx, st, "velvet_fill_kernel"); hipLaunchKernelGGL(velvet_fill_kernel, dim3(max_seg), dim3(256), 0, st, d_ss, d_sl, d_ns, n, seed, d_vel); }
-  WH_LAUNCH_CHECK("velvet_fill_kernel");
+  WH_LAUNCH(ctx, st, "velvet_layout_kernel", velvet_layout_kernel, dim3(1), dim3(64), 0, n, lens[0], lens[1], lens[2],
+            seed, max_seg, d_ss, d_sl, d_ns);
+  WH_LAUNCH(ctx, st, "velvet_fill_kernel", velvet_fill_kernel, dim3(max_seg), dim3(256), 0, d_ss, d_sl, d_ns, n, seed,
+            d_vel);
   const size_t lds = sizeof(double) * (fft_size / 2 + 1);
-  { wh::KernelTimer _kt(ctx, st, "seed_pulse_kernel"); hipLaunchKernelGGL(seed_pulse_kernel, dim3(n_bands), dim3(256), lds, st, fs, fft_size, n_bands, pulse_seed); }
-  WH_LAUNCH_CHECK("seed_pulse_kernel");
-  { wh::KernelTimer _kt(ctx, st, "seed_noise_kernel"); hipLaunchKernelGGL(seed_noise_kernel, dim3((n + 255) / 256, n_bands), dim3(256), 0, st, d_vel, n, pulse_seed, fft_size, n_bands, noise_seed); }
-  WH_LAUNCH_CHECK("seed_noise_kernel");
-  { wh::KernelTimer _kt(ctx, st, "seed_band0_dc_kernel"); hipLaunchKernelGGL(seed_band0_dc_kernel, dim3(1), dim3(256), 0, st, fft_size, n_bands, pulse_seed); }
-  WH_LAUNCH_CHECK("seed_band0_dc_kernel");
+  WH_LAUNCH(ctx, st, "seed_pulse_kernel", seed_pulse_kernel, dim3(n_bands), dim3(256), lds, fs, fft_size, n_bands,
+            pulse_seed);
+  WH_LAUNCH(ctx, st, "seed_noise_kernel", seed_noise_kernel, dim3((n + 255) / 256, n_bands), dim3(256), 0, d_vel, n,
+            pulse_seed, fft_size, n_bands, noise_seed);
+  WH_LAUNCH(ctx, st, "seed_band0_dc_kernel", seed_band0_dc_kernel, dim3(1), dim3(256), 0, fft_size, n_bands,
+            pulse_seed);
   if (velvet_out) WH_CHECK(hipMemcpyAsync(velvet_out, d_vel, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
   return 0;
 }

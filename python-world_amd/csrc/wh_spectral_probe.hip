@@ -47,15 +47,6 @@ __global__ __launch_bounds__(FT) void spectral_probe_kernel(const double* __rest
   }
 }
 
-template <int N, int FT>
-int launch(hipStream_t st, int which, double fs, const double* f0, const double* rh, const double* in, double* out, long long count) {
-  const size_t lds = sizeof(double) * ((N + 2) + (N / 2 + 2) + 32);
-  if (int rc = wh::allow_lds(&spectral_probe_kernel<N, FT>, lds)) return rc;
-  hipLaunchKernelGGL((spectral_probe_kernel<N, FT>), dim3((unsigned)count), dim3(FT), lds, st, in, out, f0, rh, which, fs, count);
-  WH_LAUNCH_CHECK("spectral_probe_kernel");
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int wh_spectral_probe(wh_ctx* ctx, void* stream, int n, int ft, int which, double fs, const double* f0,
@@ -66,10 +57,18 @@ extern "C" int wh_spectral_probe(wh_ctx* ctx, void* stream, int n, int ft, int w
   WH_ENTER(ctx);
   if (count == 0) return 0;
   const hipStream_t st = (hipStream_t)stream;
-#define WH_SPECTRAL_CASE(N_, FT_) \
-  if (n == N_ && ft == FT_) return launch<N_, FT_>(st, which, fs, f0, reach_or_half, in, out, (long long)count);
   // cheaptrick_kernel's (N, FT): 128 threads up to N = 1024, 256 from N = 2048
-  WH_SPECTRAL_CASE(256, 128) WH_SPECTRAL_CASE(512, 128) WH_SPECTRAL_CASE(1024, 128) WH_SPECTRAL_CASE(2048, 256) WH_SPECTRAL_CASE(4096, 256)
-#undef WH_SPECTRAL_CASE
-  return wh::fail_msg("wh_spectral_probe", "shape (n, ft) not built: CheapTrick's (256 | 512 | 1024, 128) and (2048 | 4096, 256)");
+  const auto kernel = n == 256 && ft == 128    ? spectral_probe_kernel<256, 128>
+                      : n == 512 && ft == 128  ? spectral_probe_kernel<512, 128>
+                      : n == 1024 && ft == 128 ? spectral_probe_kernel<1024, 128>
+                      : n == 2048 && ft == 256 ? spectral_probe_kernel<2048, 256>
+                      : n == 4096 && ft == 256 ? spectral_probe_kernel<4096, 256>
+                                               : nullptr;
+  if (!kernel)
+    return wh::fail_msg("wh_spectral_probe", "shape (n, ft) not built: CheapTrick's (256 | 512 | 1024, 128) and (2048 | 4096, 256)");
+  const size_t lds = sizeof(double) * ((n + 2) + (n / 2 + 2) + 32);
+  if (int rc = wh::allow_lds(kernel, lds)) return rc;
+  WH_LAUNCH_UNTIMED(st, "spectral_probe_kernel", kernel, dim3((unsigned)count), dim3(ft), lds, in, out, f0,
+                    reach_or_half, which, fs, count);
+  return 0;
 }

@@ -421,17 +421,13 @@ extern "C" int wh_stonemask(wh_ctx* ctx, void* stream, const wh_batch* b, const 
     uint8_t* d_todo = reinterpret_cast<uint8_t*>(ctx->ws);
     const size_t lds_tab = sizeof(double2) * (size_t)tw_n;
     const long long n_blocks = (b->total_frames + 256 / kSmLanes - 1) / (256 / kSmLanes);
-    {
-      wh::KernelTimer _kt(ctx, st, "stonemask_tab_kernel");
-      hipLaunchKernelGGL(stonemask_tab_kernel, dim3((unsigned)wh::xcd_grid(n_blocks)), dim3(256), lds_tab, st, x, b->d_x_off,
-                         b->d_frame_utt, tp, f0, refined_f0, fs, kmax, d_wtab, d_qt, ctx->d_twiddle, tw_n, d_todo,
-                         (long long)b->total_frames);
-    }
-    WH_LAUNCH_CHECK("stonemask_tab_kernel");
+    WH_LAUNCH(ctx, st, "stonemask_tab_kernel", stonemask_tab_kernel, dim3((unsigned)wh::xcd_grid(n_blocks)), dim3(256),
+              lds_tab, x, b->d_x_off, b->d_frame_utt, tp, f0, refined_f0, fs, kmax, d_wtab, d_qt, ctx->d_twiddle, tw_n,
+              d_todo, b->total_frames);
     d_only = d_todo;
   }
-  { wh::KernelTimer _kt(ctx, st, "stonemask_kernel"); hipLaunchKernelGGL(stonemask_kernel, dim3((unsigned)wh::xcd_grid(b->total_frames)), dim3(64), lds, st, x, b->d_x_off,
-                     b->d_frame_utt, tp, f0, refined_f0, fs, d_qt, kmax, ctx->d_twiddle, err, d_only, (long long)b->total_frames); }
-  WH_LAUNCH_CHECK("stonemask_kernel");
+  WH_LAUNCH(ctx, st, "stonemask_kernel", stonemask_kernel, dim3((unsigned)wh::xcd_grid(b->total_frames)), dim3(64), lds,
+            x, b->d_x_off, b->d_frame_utt, tp, f0, refined_f0, fs, d_qt, kmax, ctx->d_twiddle, err, d_only,
+            b->total_frames);
   return 0;
 }

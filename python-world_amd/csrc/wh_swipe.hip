@@ -171,14 +171,22 @@ __global__ __launch_bounds__(64) void swipe_pick_kernel(const double* __restrict
   vuv[t] = voiced ? 1.0 : 0.0;
 }
 
-template <int WS>
-int launch_stft(hipStream_t st, int64_t total_seg, const double* x, const SwUtt* d_meta, int B, const double* d_win, int hop,
-                const double2* tw, double* mag) {
-  constexpr int NT = WS >= 512 ? 256 : WS / 2;
-  const size_t lds = sizeof(double) * (WS + 2);
-  if (int rc = wh::allow_lds(&swipe_stft_kernel<WS>, lds)) return rc;
-  hipLaunchKernelGGL(swipe_stft_kernel<WS>, dim3((unsigned)total_seg), dim3(NT), lds, st, x, d_meta, B, d_win, hop, tw, mag);
-  return 0;
+// swipe_stft_kernel<WS> of a window size, a power of two in [64, 16384]; it runs on WS >= 512 ? 256 : WS / 2 threads with
+// WS + 2 doubles of LDS
+decltype(&swipe_stft_kernel<64>) stft_kernel(int ws) {
+  switch (ws) {
+    case 64: return swipe_stft_kernel<64>;
+    case 128: return swipe_stft_kernel<128>;
+    case 256: return swipe_stft_kernel<256>;
+    case 512: return swipe_stft_kernel<512>;
+    case 1024: return swipe_stft_kernel<1024>;
+    case 2048: return swipe_stft_kernel<2048>;
+    case 4096: return swipe_stft_kernel<4096>;
+    // (8 fs / f0_floor rounds to 2^13 from 88.2 kHz up at the default floor, and for floors below ~60 Hz at 44.1 / 48 kHz)
+    case 8192: return swipe_stft_kernel<8192>;
+    // (and to 2^14 below ~66 Hz at 88.2 / 96 kHz: a real transform of 16384 samples is the 8192-point complex one D4C runs at 96 kHz)
+    default: return swipe_stft_kernel<16384>;
+  }
 }
 
 }  // namespace
@@ -244,34 +252,20 @@ extern "C" int wh_swipe(wh_ctx* ctx, void* stream, const wh_batch* b, const doub
     if (int rc = wh::persistent_upload(ctx, st, "swipe.win" + tag, win, &d_win)) return rc;
     if (int rc = wh::persistent_upload(ctx, st, "swipe.mu" + tag, mu, &d_mu)) return rc;
     const int64_t total_seg = metas[i][B - 1].seg_off + metas[i][B - 1].nseg;
-    {
-      wh::KernelTimer _kt(ctx, st, "swipe_stft_kernel");
-      int rc_stft = 0;
-      switch (w.ws) {
-        case 64: rc_stft = launch_stft<64>(st, total_seg, x, d_meta, B, d_win, w.hop, ctx->d_twiddle, d_mag); break;
-        case 128: rc_stft = launch_stft<128>(st, total_seg, x, d_meta, B, d_win, w.hop, ctx->d_twiddle, d_mag); break;
-        case 256: rc_stft = launch_stft<256>(st, total_seg, x, d_meta, B, d_win, w.hop, ctx->d_twiddle, d_mag); break;
-        case 512: rc_stft = launch_stft<512>(st, total_seg, x, d_meta, B, d_win, w.hop, ctx->d_twiddle, d_mag); break;
-        case 1024: rc_stft = launch_stft<1024>(st, total_seg, x, d_meta, B, d_win, w.hop, ctx->d_twiddle, d_mag); break;
-        case 2048: rc_stft = launch_stft<2048>(st, total_seg, x, d_meta, B, d_win, w.hop, ctx->d_twiddle, d_mag); break;
-        case 4096: rc_stft = launch_stft<4096>(st, total_seg, x, d_meta, B, d_win, w.hop, ctx->d_twiddle, d_mag); break;
-        // (8 fs / f0_floor rounds to 2^13 from 88.2 kHz up at the default floor, and for floors below ~60 Hz at 44.1 / 48 kHz)
-        case 8192: rc_stft = launch_stft<8192>(st, total_seg, x, d_meta, B, d_win, w.hop, ctx->d_twiddle, d_mag); break;
-        // (and to 2^14 below ~66 Hz at 88.2 / 96 kHz: a real transform of 16384 samples is the 8192-point complex one D4C runs at 96 kHz)
-        default: rc_stft = launch_stft<16384>(st, total_seg, x, d_meta, B, d_win, w.hop, ctx->d_twiddle, d_mag); break;
-      }
-      if (rc_stft) return rc_stft;
-    }
-    WH_LAUNCH_CHECK("swipe_stft_kernel");
+    const auto stft = stft_kernel(w.ws);
+    const size_t lds_stft = sizeof(double) * (w.ws + 2);
+    if (int rc = wh::allow_lds(stft, lds_stft)) return rc;
+    WH_LAUNCH(ctx, st, "swipe_stft_kernel", stft, dim3((unsigned)total_seg), dim3(w.ws >= 512 ? 256 : w.ws / 2),
+              lds_stft, x, d_meta, B, d_win, w.hop, ctx->d_twiddle, d_mag);
     const int nbins = w.ws / 2 + 1;
     // loudness = sqrt(max(0, spline resampling of the magnitude row))            (epilogue 3)
     const uint64_t tag_i = w.table_tag ? w.table_tag * 2 + 1 : 0, tag_k = w.table_tag ? w.table_tag * 2 + 2 : 0;
     if (int rc = wh_feature_matmul_tagged(ctx, stream, d_mag, total_seg, nbins, nbins, 0, nullptr, 1.0, w.h_interp, n_erb, 3, d_L, n_erb, tag_i)) return rc;
-    { wh::KernelTimer _kt(ctx, st, "swipe_normalise_kernel"); hipLaunchKernelGGL(swipe_normalise_kernel, dim3((unsigned)total_seg), dim3(256), 0, st, d_L, total_seg, n_erb); }
-    WH_LAUNCH_CHECK("swipe_normalise_kernel");
+    WH_LAUNCH(ctx, st, "swipe_normalise_kernel", swipe_normalise_kernel, dim3((unsigned)total_seg), dim3(256), 0, d_L,
+              total_seg, n_erb);
     if (int rc = wh_feature_matmul_tagged(ctx, stream, d_L, total_seg, n_erb, n_erb, 0, nullptr, 1.0, w.h_kernels, w.n_c, 0, d_si, w.n_c, tag_k)) return rc;
-    { wh::KernelTimer _kt(ctx, st, "swipe_accumulate_kernel"); hipLaunchKernelGGL(swipe_accumulate_kernel, dim3((unsigned)((max_nf + 3) / 4), B), dim3(256), 0, st, d_meta, d_si, w.n_c, w.j0, d_mu, w.ws, w.hop, fs, dt, n_cand, d_S); }
-    WH_LAUNCH_CHECK("swipe_accumulate_kernel");
+    WH_LAUNCH(ctx, st, "swipe_accumulate_kernel", swipe_accumulate_kernel, dim3((unsigned)((max_nf + 3) / 4), B),
+              dim3(256), 0, d_meta, d_si, w.n_c, w.j0, d_mu, w.ws, w.hop, fs, dt, n_cand, d_S);
   }
   std::vector<double> pc(h_pc, h_pc + n_cand), ntc(h_ntc, h_ntc + (size_t)n_cand * 3), fine(h_fine, h_fine + (size_t)n_cand * kFine);
   std::vector<int32_t> nfine(h_n_fine, h_n_fine + n_cand);
@@ -281,7 +275,7 @@ extern "C" int wh_swipe(wh_ctx* ctx, void* stream, const wh_batch* b, const doub
   if (int rc = wh::persistent_upload(ctx, st, "swipe.ntc", ntc, &d_ntc)) return rc;
   if (int rc = wh::persistent_upload(ctx, st, "swipe.fine", fine, &d_fine)) return rc;
   if (int rc = wh::persistent_upload(ctx, st, "swipe.nfine", nfine, &d_nf)) return rc;
-  { wh::KernelTimer _kt(ctx, st, "swipe_pick_kernel"); hipLaunchKernelGGL(swipe_pick_kernel, dim3((unsigned)b->total_frames), dim3(64), 0, st, d_S, (int64_t)b->total_frames, n_cand, d_pc, d_ntc, d_fine, d_nf, s_thr, f0_out, vuv_out); }
-  WH_LAUNCH_CHECK("swipe_pick_kernel");
+  WH_LAUNCH(ctx, st, "swipe_pick_kernel", swipe_pick_kernel, dim3((unsigned)b->total_frames), dim3(64), 0, d_S,
+            b->total_frames, n_cand, d_pc, d_ntc, d_fine, d_nf, s_thr, f0_out, vuv_out);
   return 0;
 }

@@ -347,17 +347,19 @@ int launch_resp(wh_ctx* ctx, hipStream_t st, const RespCall& c) {
   if (int rc = wh::persistent_scratch(ctx, "syn.ola_rows", sizeof(double) * (size_t)row_base[B], &d_rows)) return rc;
   if (int rc = wh::persistent_scratch(ctx, "syn.run_base", sizeof(int64_t) * ((size_t)B + 1), &d_rb)) return rc;
   if (int rc = wh::persistent_scratch(ctx, "syn.row_off", sizeof(int64_t) * (size_t)runs_cap * B, &d_ro)) return rc;
-  { wh::KernelTimer _kt(ctx, st, "pulse_run_base_kernel"); hipLaunchKernelGGL(pulse_run_base_kernel, dim3(1), dim3(64), 0, st, p_count, B, resp_run(N), reinterpret_cast<int64_t*>(d_rb)); }
-  WH_LAUNCH_CHECK("pulse_run_base_kernel");
-  { wh::KernelTimer _kt(ctx, st, "pulse_rows_kernel"); hipLaunchKernelGGL(pulse_rows_kernel<N>, dim3(B), dim3(256), 0, st, d_meta, p_idx, p_count, runs_cap, d_row_base, reinterpret_cast<int64_t*>(d_ro), ctx->d_flags); }
-  WH_LAUNCH_CHECK("pulse_rows_kernel");
+  WH_LAUNCH(ctx, st, "pulse_run_base_kernel", pulse_run_base_kernel, dim3(1), dim3(64), 0, p_count, B, resp_run(N),
+            reinterpret_cast<int64_t*>(d_rb));
+  WH_LAUNCH(ctx, st, "pulse_rows_kernel", pulse_rows_kernel<N>, dim3(B), dim3(256), 0, d_meta, p_idx, p_count, runs_cap,
+            d_row_base, reinterpret_cast<int64_t*>(d_ro), ctx->d_flags);
   // one workgroup per run of resp_run(N) pulse slots; runs past the real pulse count exit at once
   const int64_t grid = wh::xcd_grid(runs_cap * B);
-  { wh::KernelTimer _kt(ctx, st, "response_kernel"); RespArgs ra{d_meta, c.tp, c.spec, c.ap, c.fs, c.p_rec, c.p_base, B, c.noise, c.seed, d_dc, ctx->d_twiddle, d_mt, reinterpret_cast<double*>(d_rows), d_row_base, reinterpret_cast<const int64_t*>(d_rb), reinterpret_cast<const int64_t*>(d_ro), runs_cap};
-  hipLaunchKernelGGL(response_kernel<N>, dim3((unsigned)grid), dim3(ft_syn(N)), lds, st, ra); }
-  WH_LAUNCH_CHECK("response_kernel");
-  { wh::KernelTimer _kt(ctx, st, "response_gather_kernel"); hipLaunchKernelGGL(response_gather_kernel<N>, dim3((unsigned)((max_ny + kGatherTile - 1) / kGatherTile), B), dim3(256), 0, st, d_meta, p_idx, p_count, reinterpret_cast<const double*>(d_rows), d_row_base, reinterpret_cast<const int64_t*>(d_ro), runs_cap, c.y); }
-  WH_LAUNCH_CHECK("response_gather_kernel");
+  const RespArgs ra{d_meta, c.tp, c.spec, c.ap, c.fs, c.p_rec, c.p_base, B, c.noise, c.seed, d_dc, ctx->d_twiddle, d_mt,
+                    reinterpret_cast<double*>(d_rows), d_row_base, reinterpret_cast<const int64_t*>(d_rb),
+                    reinterpret_cast<const int64_t*>(d_ro), runs_cap};
+  WH_LAUNCH(ctx, st, "response_kernel", response_kernel<N>, dim3((unsigned)grid), dim3(ft_syn(N)), lds, ra);
+  WH_LAUNCH(ctx, st, "response_gather_kernel", response_gather_kernel<N>,
+            dim3((unsigned)((max_ny + kGatherTile - 1) / kGatherTile), B), dim3(256), 0, d_meta, p_idx, p_count,
+            reinterpret_cast<const double*>(d_rows), d_row_base, reinterpret_cast<const int64_t*>(d_ro), runs_cap, c.y);
   return 0;
 }
 
@@ -391,11 +393,9 @@ extern "C" int wh_synthesis_render(wh_ctx* ctx, void* stream, const wh_batch* b,
   const int64_t* d_pi = reinterpret_cast<const int64_t*>(ws + t.o_pi);
   const PulseRec* d_rec = reinterpret_cast<const PulseRec*>(ws + t.o_rec);
   const int32_t* d_pc = reinterpret_cast<const int32_t*>(ws + t.o_pc);
-  if (noise) {  // (the time base knows nothing about the noise stream: the cover test belongs to the call that is given one)
-    wh::KernelTimer _kt(ctx, st, "noise_cover_kernel");
-    hipLaunchKernelGGL(noise_cover_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, d_meta, d_rec, d_pb, B, ctx->d_flags);
-  }
-  WH_LAUNCH_CHECK("noise_cover_kernel");
+  if (noise)  // (the time base knows nothing about the noise stream: the cover test belongs to the call that is given one)
+    WH_LAUNCH(ctx, st, "noise_cover_kernel", noise_cover_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, d_meta,
+              d_rec, d_pb, B, ctx->d_flags);
   std::vector<int64_t> h_ny((size_t)B);
   for (int u = 0; u < B; ++u) h_ny[u] = meta[u].ny;
   const RespCall call{B, pulse_cap, max_ny, &h_ny, d_meta, tp, spectrogram, aperiodicity, fs, d_rec, d_pb, d_pi, d_pc, noise, seed, y};
@@ -430,8 +430,8 @@ extern "C" int wh_philox_normals(wh_ctx* ctx, void* stream, uint64_t seed, int u
   WH_ENTER(ctx);
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  { wh::KernelTimer _kt(ctx, st, "philox_dump_kernel"); hipLaunchKernelGGL(philox_dump_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, seed, (int32_t)utt, q0, n, out); }
-  WH_LAUNCH_CHECK("philox_dump_kernel");
+  WH_LAUNCH(ctx, st, "philox_dump_kernel", philox_dump_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, seed,
+            (int32_t)utt, q0, n, out);
   return 0;
 }
 

@@ -424,8 +424,8 @@ int wh::exact_cumsum_segments(wh_ctx* ctx, hipStream_t st, double* d_data, const
   if (!s_pairs.empty()) {
     int64_t* d_sp = nullptr;
     if (int rc = wh::persistent_upload(ctx, st, "cumsum.short", s_pairs, &d_sp)) return rc;
-    { wh::KernelTimer _kt(ctx, st, "phase_kernel"); hipLaunchKernelGGL(exact_cumsum_pairs_kernel, dim3((unsigned)(s_pairs.size() / 2)), dim3(kXThreads), 0, st, d_data, d_sp); }
-    WH_LAUNCH_CHECK("exact_cumsum_pairs_kernel");
+    WH_LAUNCH(ctx, st, "phase_kernel", exact_cumsum_pairs_kernel, dim3((unsigned)(s_pairs.size() / 2)), dim3(kXThreads),
+              0, d_data, d_sp);
   }
   if (l_pairs.empty()) return 0;
   const int ns = (int)(l_pairs.size() / 2);
@@ -438,12 +438,16 @@ int wh::exact_cumsum_segments(wh_ctx* ctx, hipStream_t st, double* d_data, const
   double* d_S = reinterpret_cast<double*>(d_scr);
   double* d_C = d_S + nt;
   XsTile* d_tiles = reinterpret_cast<XsTile*>(d_C + nt);
-  { wh::KernelTimer _kt(ctx, st, "xs_tile_sum_kernel"); hipLaunchKernelGGL(xs_tile_sum_kernel, dim3((unsigned)nt), dim3(256), 0, st, d_data, d_lp, d_tb, ns, d_S); }
-  { wh::KernelTimer _kt(ctx, st, "xs_prefix_kernel"); hipLaunchKernelGGL(xs_prefix_kernel, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, st, d_tb, ns, d_S); }
-  { wh::KernelTimer _kt(ctx, st, "xs_tile_total_kernel"); hipLaunchKernelGGL(xs_tile_total_kernel, dim3((unsigned)nt), dim3(256), 0, st, d_data, d_lp, d_tb, ns, d_S, d_tiles); }
-  { wh::KernelTimer _kt(ctx, st, "xs_carry_kernel"); hipLaunchKernelGGL(xs_carry_kernel, dim3((unsigned)ns), dim3(kXThreads), 0, st, d_data, d_lp, d_tb, d_tiles, d_C); }
-  { wh::KernelTimer _kt(ctx, st, "xs_apply_kernel"); hipLaunchKernelGGL(xs_apply_kernel, dim3((unsigned)nt), dim3(256), 0, st, d_data, d_lp, d_tb, ns, d_tiles, d_C); }
-  WH_LAUNCH_CHECK("xs_apply_kernel");
+  WH_LAUNCH(ctx, st, "xs_tile_sum_kernel", xs_tile_sum_kernel, dim3((unsigned)nt), dim3(256), 0, d_data, d_lp, d_tb, ns,
+            d_S);
+  WH_LAUNCH(ctx, st, "xs_prefix_kernel", xs_prefix_kernel, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, d_tb, ns,
+            d_S);
+  WH_LAUNCH(ctx, st, "xs_tile_total_kernel", xs_tile_total_kernel, dim3((unsigned)nt), dim3(256), 0, d_data, d_lp, d_tb,
+            ns, d_S, d_tiles);
+  WH_LAUNCH(ctx, st, "xs_carry_kernel", xs_carry_kernel, dim3((unsigned)ns), dim3(kXThreads), 0, d_data, d_lp, d_tb,
+            d_tiles, d_C);
+  WH_LAUNCH(ctx, st, "xs_apply_kernel", xs_apply_kernel, dim3((unsigned)nt), dim3(256), 0, d_data, d_lp, d_tb, ns,
+            d_tiles, d_C);
   return 0;
 }
 namespace {
@@ -668,21 +672,20 @@ int wh::launch_pulses(wh_ctx* ctx, hipStream_t st, int B, int64_t max_ny, const 
   double* d_ps = reinterpret_cast<double*>(ws + lay.o_ps);
   int64_t* d_pn = reinterpret_cast<int64_t*>(ws + lay.o_pn);
   int32_t* d_pc = reinterpret_cast<int32_t*>(ws + lay.o_pc);
-  { wh::KernelTimer _kt(ctx, st, "prep_kernel"); hipLaunchKernelGGL(prep_kernel, dim3((unsigned)((max_ny + 255) / 256), B), dim3(256), 0, st, d_meta, tp, f0, vuv, fs,
-                     f0_low_limit, d_phase, d_vuv); }
-  WH_LAUNCH_CHECK("prep_kernel");
+  WH_LAUNCH(ctx, st, "prep_kernel", prep_kernel, dim3((unsigned)((max_ny + 255) / 256), B), dim3(256), 0, d_meta, tp,
+            f0, vuv, fs, f0_low_limit, d_phase, d_vuv);
   if (int rc = exact_cumsum_segments(ctx, st, d_phase, h_y_off, B)) return rc;
   const int mt = pulse_tiles(max_ny);
   uint8_t* d_masks = reinterpret_cast<uint8_t*>(ws + lay.o_px);
   int32_t* d_tc = reinterpret_cast<int32_t*>(ws + lay.o_px + (((size_t)B * mt * 256 + 255) & ~(size_t)255));
-  { wh::KernelTimer _kt(ctx, st, "pulse_mark_kernel"); hipLaunchKernelGGL(pulse_mark_kernel, dim3(mt, B), dim3(256), 0, st, d_meta, d_phase, mt, d_masks, d_tc); }
-  WH_LAUNCH_CHECK("pulse_mark_kernel");
-  { wh::KernelTimer _kt(ctx, st, "pulse_scan_kernel"); hipLaunchKernelGGL(pulse_scan_kernel, dim3(B), dim3(256), 0, st, d_meta, mt, d_tc, d_pc, ctx->d_flags); }
-  WH_LAUNCH_CHECK("pulse_scan_kernel");
-  { wh::KernelTimer _kt(ctx, st, "pulse_emit_kernel"); hipLaunchKernelGGL(pulse_emit_kernel, dim3(mt, B), dim3(256), 0, st, d_meta, mt, d_masks, d_tc, fs, d_pt, d_pi); }
-  WH_LAUNCH_CHECK("pulse_emit_kernel");
-  { wh::KernelTimer _kt(ctx, st, "pulse_finish_kernel"); hipLaunchKernelGGL(pulse_finish_kernel, dim3(B), dim3(kPFinish), 0, st, d_meta, d_phase, fs, d_pi, d_pc, d_ps, d_pn, ctx->d_flags); }
-  WH_LAUNCH_CHECK("pulse_finish_kernel");
+  WH_LAUNCH(ctx, st, "pulse_mark_kernel", pulse_mark_kernel, dim3(mt, B), dim3(256), 0, d_meta, d_phase, mt, d_masks,
+            d_tc);
+  WH_LAUNCH(ctx, st, "pulse_scan_kernel", pulse_scan_kernel, dim3(B), dim3(256), 0, d_meta, mt, d_tc, d_pc,
+            ctx->d_flags);
+  WH_LAUNCH(ctx, st, "pulse_emit_kernel", pulse_emit_kernel, dim3(mt, B), dim3(256), 0, d_meta, mt, d_masks, d_tc, fs,
+            d_pt, d_pi);
+  WH_LAUNCH(ctx, st, "pulse_finish_kernel", pulse_finish_kernel, dim3(B), dim3(kPFinish), 0, d_meta, d_phase, fs, d_pi,
+            d_pc, d_ps, d_pn, ctx->d_flags);
   return 0;
 }
 
@@ -743,11 +746,10 @@ extern "C" int wh_synthesis_timebase(wh_ctx* ctx, void* stream, const wh_batch* 
   const int32_t* d_pc = reinterpret_cast<const int32_t*>(ws + lay.o_pc);
   if (int rc = wh::persistent_upload(ctx, st, "syn.tbmeta", meta, &d_meta)) return rc;
   if (int rc = wh::launch_pulses(ctx, st, B, max_ny, d_meta, tp, f0, vuv, fs, f0_low_limit, h_y_off, ws, lay)) return rc;
-  { wh::KernelTimer _kt(ctx, st, "pulse_base_kernel"); hipLaunchKernelGGL(pulse_base_kernel, dim3(1), dim3(64), 0, st, d_pc, B, d_pb); }
-  WH_LAUNCH_CHECK("pulse_base_kernel");
-  { wh::KernelTimer _kt(ctx, st, "pulse_frames_kernel"); hipLaunchKernelGGL(pulse_frames_kernel, dim3((unsigned)((pulse_cap + 255) / 256), B), dim3(256), 0, st, d_meta, tp, d_pt, d_pi, d_ps, d_pn, d_vuv, d_pc, d_pb,
-                     reinterpret_cast<PulseRec*>(ws + o_rec)); }
-  WH_LAUNCH_CHECK("pulse_frames_kernel");
+  WH_LAUNCH(ctx, st, "pulse_base_kernel", pulse_base_kernel, dim3(1), dim3(64), 0, d_pc, B, d_pb);
+  WH_LAUNCH(ctx, st, "pulse_frames_kernel", pulse_frames_kernel, dim3((unsigned)((pulse_cap + 255) / 256), B),
+            dim3(256), 0, d_meta, tp, d_pt, d_pi, d_ps, d_pn, d_vuv, d_pc, d_pb,
+            reinterpret_cast<PulseRec*>(ws + o_rec));
   wh_ctx::TimeBase& t = ctx->timebase;
   t.valid = true;
   t.n_utt = B;

@@ -26,6 +26,24 @@ def test_library_exports_every_declared_symbol():
     assert lib.wh_d4c_bands(16000.0, 0) == 1 and lib.wh_d4c_bands(48000.0, 1) == 5
 
 
+def test_every_launch_goes_through_the_helper():
+    """wh::launch / WH_LAUNCH (csrc/wh_host.h) is the one place that brackets a kernel for the profile, launches it and
+    reads the runtime's error: no other file launches by hand, times by hand or checks by hand."""
+    import glob
+
+    csrc = os.path.join(ROOT, "python-world_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(files) > 40 and os.path.join(csrc, "wh_host.h") in files
+    raw = ("hipLaunchKernelGGL", "<<<", "KernelTimer", "WH_LAUNCH_CHECK", "hipGetLastError")
+    found = []
+    for path in files:
+        if os.path.basename(path) == "wh_host.h":
+            continue
+        text = open(path).read()
+        found += [(os.path.basename(path), word) for word in raw if word in text]
+    assert not found, found
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
 
