@@ -621,6 +621,40 @@ int wh_lsf_distortion(wh_ctx* ctx, void* stream, const double* rows_a, int64_t n
                       int64_t n_rows_b, int64_t ldb, int p, const int64_t* idx_a, const int64_t* idx_b, int64_t n_pairs,
                       const double* h_cos, int k_bins, double* out);
 
+/* ---- A per-frame spectral gain applied to a waveform: vocoder-free conversion (no counterpart in the reference's library) -- */
+/* ABI 121; tests/_specfilter_reference.py is the same contract in NumPy.  The recording is cut into
+ * Hanning windows on an integer hop, every window's spectrum is multiplied by the minimum-phase spectrum of a log-gain
+ * row, and the responses are overlap-added: the frame loop of world/synthesisRequiem.py:74-101 as a filter for recordings.
+ * Per utterance u: ny = h_x_off[u+1] - h_x_off[u] samples, F = h_frame_off[u+1] - h_frame_off[u] gain rows (rows
+ * h_frame_off[u] .. of num and den), H = h_hop[u] >= 1 with 2 H - 1 <= fft_size = N, K = N / 2 + 1.
+ *   windows   W = ceil(ny / H) + 1 (an empty utterance: none), w = 0 .. W-1; window w starts at the 0-based sample
+ *             s_w = w H - H (centre w H - 1: synthesisRequiem.py:84);  win[j] = 0.5 - 0.5 cospi(2 (j + 1) / (2 H)),
+ *             j < 2 H - 1 (win[j] + win[j + H] = 1).
+ *   row map   window w uses gain row h_map[h_map_off[u] + w] of the utterance (HOST int32; h_map_off[u+1] - h_map_off[u]
+ *             must be W); an entry outside [0, F) is an argument error.
+ *   segment   seg[j] = x[s_w + j] * win[j] where 0 <= s_w + j < ny, else 0, zero-padded to N.  Nothing is clipped.
+ *   gain      h[k], k < K, the half log power ratio of row r = map[w]:
+ *             kind 0 (spectrum; p_or_kbins = K, rows of K bins): h = (log|num[r][k]| - log|den[r][k]|) / 2;
+ *               den == NULL: h = log|num[r][k]| / 2.
+ *             kind 1 (lsf; p_or_kbins = p, even, 2 .. 64; rows [log E, x_1 .. x_p], x = cos w descending, as
+ *               wh_lsf_envelope takes them but with the LOG of the gain in column 0): per bin, c = h_cos[k] (HOST [K],
+ *               cos(pi k / (K - 1))), A2 of each side exactly as wh_lsf_distortion forms it;
+ *               h = ((logE_n - logE_d) - log(A2_n / A2_d)) / 2;  den == NULL: h = (logE_n - log A2_n) / 2.
+ *             G_w = the minimum-phase spectrum of h: cepstrum of the mirrored h, fold (bin 0 kept, upper half doubled,
+ *             lower half zeroed), exp of the inverse transform (synthesisRequiem.py:112-118).
+ *   response  r_w = irfft(rfft(seg) * G_w), N real taps, circular;  y[t] = the sum over the windows with
+ *             0 <= t - s_w < N of r_w[t - s_w], 0 <= t < ny.  Taps outside the utterance are dropped.
+ * Not part of the contract: the order of that sum and the fusing inside the transforms (results are compared at
+ * tolerances, as for wh_synthesis_requiem).  Part of it: no atomics — the same bits from run to run, and for an
+ * utterance alone as inside any batch; non-finite or non-positive gain entries flow through (a NaN in gain row r
+ * reaches the samples [s_w, s_w + N) of the windows with map[w] == r and nothing else); no index or trip count
+ * depends on a value.  num, den (ldn, ldd: doubles between rows), x, y: DEVICE, FP64; y in x's layout, y must not
+ * overlap x.  h_cos may be NULL for kind 0.  n_utt == 0 is no error; wrong arguments fail before anything is launched. */
+int wh_spectral_filter(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_off, const int64_t* h_frame_off,
+                       const int64_t* h_map_off, const int32_t* h_map, const int64_t* h_hop, int kind, const double* num,
+                       int64_t ldn, const double* den, int64_t ldd, int p_or_kbins, const double* h_cos, int fft_size,
+                       const double* x, double* y);
+
 /* ---- 16-bit PCM at the batch boundary (the reference's WAV usage: example/prosody.py:12-13,57) ---------------------- */
 /* x[i] = pcm[i] / (2^15 - 1); pcm[i] = int16(trunc(y[i] * 2^15)) (low 16 bits, like NumPy's astype on the reference's
  * platform).  DEVICE pointers: the 2-byte samples cross PCIe instead of the 8-byte ones. */

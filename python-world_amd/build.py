@@ -34,6 +34,9 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 #   * wh_synthesis.hip and wh_requiem.hip are built unfused (Philox, the Requiem excitation and the gathers round like the
 #     reference) and fuse by `#pragma clang fp contract(fast)` inside min_phase_response (wh_minphase.h), response_pulse,
 #     response_pair and noise_conv_groups only (wh_resp_pulse.h, wh_resp_pair.h).
+#   * wh_specfilter.hip (the spectral filter of recordings: the Requiem filter's chain on another geometry) is built like
+#     wh_requiem.hip: unfused — the products of its LSF gain are the contract's, rounded one by one — but for
+#     min_phase_response's own pragma.
 #   * wh_peak.hip and wh_philox_probe.hip were parts of wh_synthesis.hip, which has no entry below (it contracts by
 #     pragma): they need none either.
 # The F0 stages (DIO, StoneMask, Harvest — wh_harvest.hip, wh_hv_front.hip, wh_hv_refine.hip, wh_hv_contour.hip —, SWIPE') and the synthesis TIME BASE (wh_timebase.hip: no pragma anywhere in it)

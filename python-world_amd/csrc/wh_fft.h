@@ -272,6 +272,17 @@ __device__ __forceinline__ void rfft_lds(ckp<double2> z, ckp<const double2> WH_R
   sync_lds<SNT>();
 }
 
+// The forward real transform of one analysis frame that stands beside a minimum-phase chain (wh_minphase.h): the frame
+// filters of recordings take it from here.  Only the (N, NT) pairs of that chain — 256 threads up to N = 1024, 512 beyond,
+// the shapes the Requiem filter instantiates rfft_lds with and csrc/wh_fft_probe.hip runs (kind 2) — can be instantiated,
+// so a caller of this name cannot bring a transform shape into the library that the engine's tests do not run.
+template <int N, int NT>
+__device__ __forceinline__ void rfft_frame_lds(ckp<double2> z, ckp<const double2> WH_RESTRICT tw_base) {
+  static_assert((N == 512 && NT == 256) || (N == 1024 && NT == 256) || (N == 2048 && NT == 512) || (N == 4096 && NT == 512),
+                "a shape of the minimum-phase chains: add any other to WH_PROBE_SHAPES and tests/test_hip_fft_engine.py first");
+  rfft_lds<N, NT>(z, tw_base);
+}
+
 // Inverse.  in: z[k] = X[k], k = 0..N/2: the half spectrum; the result is Re(IDFT) of its Hermitian extension
 // (imaginary parts of the DC / Nyquist bins are ignored, as taking .real of a full complex IFFT would).
 // out: z[j] = N * (x[2j], x[2j+1]), j < N/2 (unnormalised like fft_lds<.., true>: divide by N).

@@ -472,6 +472,60 @@ def convert_compact(ce, gmm, windows=CONVERSION_WINDOWS, mode="mlpg", min_gap=No
     return ce._like(rt, arrays, None if ce.tp_host is None else np.array(ce.tp_host))
 
 
+def convert_waveform(wb, batch, x_d, ce, model, windows=CONVERSION_WINDOWS, mode="mlpg", min_gap=None, hop=None):
+    """Vocoder-free conversion: convert_compact(ce, model), then the recording ``x_d`` of ``batch`` (WorldBatch.upload's
+    pair, the waveforms ``ce`` was encoded from) filtered by the converted over the source envelope, both as coded — the
+    coding error cancels in the ratio, excitation, phase and aperiodicity stay the recording's
+    (world.specfilter.differential_device).  Returns (y_d in x's layout, the converted CompactEncoding)."""
+    from .specfilter import differential_device
+
+    converted = convert_compact(ce, model, windows, mode, min_gap)
+    return differential_device(wb, batch, x_d, ce, converted, hop=hop), converted
+
+
+def convert_waveform_dict(fs, x, dat, model, mode="mlpg", lowhz=0, highhz=8000, windows=CONVERSION_WINDOWS):
+    """World.convert_waveform: the recording ``x`` that ``dat`` was encoded from, filtered by the converted over the source
+    envelope under ``model`` (both through the model's code: mel-cepstrum or line spectral frequencies): a NumPy array
+    like x."""
+    from .batch import BatchEncoding
+    from .specfilter import _lsf_cosine_rows, filter_device
+
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 1:
+        raise ValueError("convert_waveform: x must be 1-D, got shape %s" % (x.shape,))
+    if dat['fs'] != fs:
+        raise ValueError("convert_waveform: the dict was encoded at %r Hz, not at fs = %r" % (dat['fs'], fs))
+    win, _ = check_windows(windows, "convert_waveform")
+    if model.dx % len(win) or model.dx != model.dy:
+        raise ValueError("convert_waveform: a model of %d + %d columns does not hold %d windows per speaker"
+                         % (model.dx, model.dy, len(win)))
+    tp = np.asarray(dat['temporal_positions'], dtype=np.float64)
+    frame_period = round(float(tp[1] - tp[0]) * 1e9) / 1e6 if len(tp) > 1 else 5.0
+    fft_size = 2 * (int(np.shape(dat['spectrogram'])[0]) - 1)
+    rt = _hip.Runtime.get()
+    with rt.lock, rt.on_stream():
+        enc = BatchEncoding.from_dicts(rt, [dat])
+        x_d = rt.to_device(x)
+        if model.kind == "lsf":
+            from .lsf import lsf_device
+            rows = lsf_device(rt, enc.spectrogram, model.lsf_order)
+            conv = convert_lsf(rt, enc.batch, rows, model, mode, windows)
+            y = filter_device(rt, x_d, [0, len(x)], fs, frame_period, fft_size, _lsf_cosine_rows(rt, conv),
+                              _lsf_cosine_rows(rt, rows), kind="lsf")
+        else:
+            from .compact import check_compact_args
+            from .features import imcep_device
+            n0 = model.dx // len(win) + 1
+            check_compact_args(dat['fs'], fft_size, n0, "convert_waveform")
+            mc = enc.mcep(n0, lowhz, highhz)
+            conv = convert_mcep(rt, enc.batch, mc, model, mode, windows)
+            y = filter_device(rt, x_d, [0, len(x)], fs, frame_period, fft_size, imcep_device(rt, conv, fft_size),
+                              imcep_device(rt, mc, fft_size))
+        out = y.cpu().numpy()
+    rt.check_flags("convert_waveform")
+    return out
+
+
 def _fit_conversion_lsf(dats_a, dats_b, n_components, lsf_order, n_iter, radius, windows, fit_kw):
     from .align import align_device
     from .batch import BatchEncoding

@@ -544,6 +544,26 @@ class World(object):
             raise NotImplementedError("convert_voice(devices=...): run one WorldBatch per device instead")
         return convert_voice_dict(dat, model, mode, **kw)
 
+    # ---- a per-frame spectral gain on a recording: vocoder-free conversion (world/specfilter.py) -----------------------
+    @_hip.serialised
+    def filter_waveform(self, fs, x, dat_num, dat_den=None, devices=None):
+        """The recording ``x`` filtered frame by frame with the minimum-phase response of dat_num's spectrogram over
+        dat_den's (encode() dicts on x's frame grid; ``dat_den`` None: of dat_num's alone): Hanning windows on the frame
+        hop, overlap-added; excitation, phase and aperiodicity stay the recording's.  Not peak-normalised."""
+        from .specfilter import filter_waveform_numpy
+        if devices is not None:
+            raise NotImplementedError("filter_waveform(devices=...): run one WorldBatch per device instead")
+        return filter_waveform_numpy(fs, x, dat_num, dat_den)
+
+    @_hip.serialised
+    def convert_waveform(self, fs, x, dat, model, mode="mlpg", devices=None, **kw):
+        """Vocoder-free voice conversion: ``x`` (the recording ``dat`` was encoded from) filtered by the converted over
+        the source envelope under ``model`` (fit_conversion's), both as the model codes them; the source's f0 is kept."""
+        from .gmm import convert_waveform_dict
+        if devices is not None:
+            raise NotImplementedError("convert_waveform(devices=...): run one WorldBatch per device instead")
+        return convert_waveform_dict(fs, x, dat, model, mode, **kw)
+
     # ---- modification (all in place on the dict, like the reference) ------------------------------------------
     def scale_pitch(self, dat, factor):
         """world/main.py:154-162."""
