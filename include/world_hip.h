@@ -655,6 +655,35 @@ int wh_spectral_filter(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_
                        int64_t ldn, const double* den, int64_t ldd, int p_or_kbins, const double* h_cos, int fft_size,
                        const double* x, double* y);
 
+/* ---- Waveform-similarity overlap-add: the timing of a recording changed without analysis and synthesis (no counterpart) -- */
+/* ABI 122; tests/_wsola_reference.py is the same contract in NumPy.  Stretching a recording by the f0
+ * ratio with this and resampling it back by the inverse ratio (wh_resample_poly) moves its f0 and keeps its duration: the
+ * f0 transformation that vocoder-free conversion (wh_spectral_filter) needs between speakers of different pitch.
+ * Per call: an integer hop H = hop, 1 <= H <= 1024; a tolerance D = tol, 0 <= D <= 512; L = 2 H - 1; a HOST window table
+ * h_win[0 .. L) (the binder passes 0.5 - 0.5 cos(pi (j + 1) / H), the spectral filter's window: win[j] + win[j + H] = 1;
+ * the library computes no table of its own).  Per utterance u: x[0 .. n), n = h_x_off[u+1] - h_x_off[u]; the output
+ * y[0 .. n_out), n_out = h_y_off[u+1] - h_y_off[u]; M = ceil(n_out / H) + 1 frames (none when n_out == 0) and the HOST
+ * list pos[0 .. M) = h_pos[h_pos_off[u] ..], the nominal input start of every frame (h_pos_off[u+1] - h_pos_off[u] must
+ * be M).  Any int64 is a legal position: a read of x outside [0, n) is 0.0 everywhere below, nothing is clipped.
+ *   chain     delta_0 = 0;  c_m = pos[m] + delta_m.  For m >= 1 the template is t[j] = x[c_{m-1} + H + j], j < L — the
+ *             natural continuation of the frame before — and candidate d in [-D, D] is g_d[j] = x[pos[m] + d + j].
+ *   score     num = sum_j t[j] * g_d[j], den = sum_j g_d[j] * g_d[j]: each sum from +0.0, j ascending, every product and
+ *             every sum rounded on its own (no fused multiply-add);  score = num / sqrt(den) when den > 0, else 0.0
+ *             (divide and square root correctly rounded);  a NaN score counts as -inf.
+ *   choice    delta_m = the d of the greatest score; among equal scores the smallest |d|, then the negative one (a total
+ *             order: digital silence and an all-NaN frame give delta = 0).
+ *   output    with o_m = m H - H:  y[t] = sum over the frames with 0 <= t - o_m < L, m ascending, of
+ *             win[t - o_m] * x[c_m + t - o_m], from +0.0 and unfused, 0 <= t < n_out (at most two terms).
+ * Part of the contract: no atomics — the same bits from run to run, and for an utterance alone as inside any batch; the
+ * only value-dependent index is delta, confined to [-D, D]; every access is range-tested; a NaN or Inf in x reaches no other
+ * utterance.  The shifts and y are compared bit for bit with the reference.  h_*: HOST; x, y: DEVICE FP64 (y must not
+ * overlap x); delta: DEVICE int32 [h_pos_off[n_utt]], the shifts, may be NULL.  The frames of an utterance are one
+ * sequential chain (one workgroup per utterance): a small batch of long utterances leaves most of the device idle.
+ * n_utt == 0 is no error; wrong arguments (the limits, offsets that decrease, a position list of another length than M) fail
+ * before anything is launched, with the reason in wh_last_error. */
+int wh_wsola(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_off, const int64_t* h_y_off, const int64_t* h_pos_off,
+             const int64_t* h_pos, int hop, int tol, const double* h_win, const double* x, double* y, int32_t* delta);
+
 /* ---- 16-bit PCM at the batch boundary (the reference's WAV usage: example/prosody.py:12-13,57) ---------------------- */
 /* x[i] = pcm[i] / (2^15 - 1); pcm[i] = int16(trunc(y[i] * 2^15)) (low 16 bits, like NumPy's astype on the reference's
  * platform).  DEVICE pointers: the 2-byte samples cross PCIe instead of the 8-byte ones. */

@@ -564,6 +564,26 @@ class World(object):
             raise NotImplementedError("convert_waveform(devices=...): run one WorldBatch per device instead")
         return convert_waveform_dict(fs, x, dat, model, mode, **kw)
 
+    # ---- timing and pitch of a recording without analysis and synthesis: WSOLA (world/tsm.py) -------------------------
+    @_hip.serialised
+    def stretch_waveform(self, fs, x, ratio, hop=None, tol=None, devices=None):
+        """The recording ``x`` time-stretched by waveform-similarity overlap-add: round(ratio len(x)) samples, the
+        duration x ratio at the recording's own pitch (frames on an 8 ms hop moved by up to 5 ms unless told otherwise)."""
+        from .tsm import stretch_waveform_numpy
+        if devices is not None:
+            raise NotImplementedError("stretch_waveform(devices=...): run one WorldBatch per device instead")
+        return stretch_waveform_numpy(fs, x, ratio, hop, tol)
+
+    @_hip.serialised
+    def shift_pitch_waveform(self, fs, x, ratio, hop=None, tol=None, devices=None):
+        """The recording ``x`` at f0 x p / q, p / q = world.tsm.as_fraction(ratio), and its own length: stretched by p / q
+        and resampled by q / p.  The formants move with f0; vocoder-free conversion (convert_waveform) on the shifted
+        recording moves the envelope to the target."""
+        from .tsm import shift_pitch_waveform_numpy
+        if devices is not None:
+            raise NotImplementedError("shift_pitch_waveform(devices=...): run one WorldBatch per device instead")
+        return shift_pitch_waveform_numpy(fs, x, ratio, hop, tol)
+
     # ---- modification (all in place on the dict, like the reference) ------------------------------------------
     def scale_pitch(self, dat, factor):
         """world/main.py:154-162."""
