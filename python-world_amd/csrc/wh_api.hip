@@ -65,6 +65,10 @@ int ws_reserve(wh_ctx* ctx, size_t bytes) {
   ctx->ws_bytes = want;
   return 0;
 }
+int ws_reserve(wh_ctx* ctx, const Carve& layout) {
+  if (!layout.ok()) return fail_msg("ws_reserve", "a workspace region has a negative count or a size beyond size_t");
+  return ws_reserve(ctx, layout.end());
+}
 int const_table(wh_ctx* ctx, const std::string& key, const std::vector<double>& host, const double** out) {
   auto it = ctx->tables.find(key);
   if (it != ctx->tables.end()) {
@@ -106,22 +110,26 @@ int tables_make_room(wh_ctx* ctx) {
   ctx->table_bytes = 0;
   return 0;
 }
+// The slot's device buffer holds at least `bytes` afterwards; growing it synchronises the device once.
+static int persist_grow(wh_ctx::Persist& e, size_t bytes) {
+  if (e.d && e.cap >= bytes) return 0;
+  if (e.d) {
+    WH_CHECK(hipDeviceSynchronize());  // kernels of earlier calls may still use the buffer that is about to go
+    WH_CHECK(hipFree(e.d));
+    e.d = nullptr;
+  }
+  const size_t want = bytes < 256 ? 256 : bytes + bytes / 4;
+  WH_CHECK(hipMalloc(&e.d, want));
+  e.cap = want;
+  return 0;
+}
 int persistent_upload(wh_ctx* ctx, hipStream_t st, const std::string& slot, const void* host, size_t bytes, void** dptr) {
   wh_ctx::Persist& e = ctx->persist[slot];
   if (e.d && e.host.size() == bytes && (bytes == 0 || memcmp(e.host.data(), host, bytes) == 0)) {
     *dptr = e.d;
     return 0;
   }
-  if (e.cap < bytes || !e.d) {
-    if (e.d) {
-      WH_CHECK(hipDeviceSynchronize());  // kernels of earlier calls may still read the buffer that is about to go
-      WH_CHECK(hipFree(e.d));
-      e.d = nullptr;
-    }
-    const size_t want = bytes < 256 ? 256 : bytes + bytes / 4;
-    WH_CHECK(hipMalloc(&e.d, want));
-    e.cap = want;
-  }
+  if (int rc = persist_grow(e, bytes)) return rc;
   if (bytes) {
     const int k = e.next_stage;
     e.next_stage = (k + 1) % wh_ctx::Persist::kStages;
@@ -148,16 +156,7 @@ void* persistent_resident(wh_ctx* ctx, const std::string& slot, size_t bytes) {
 }
 int persistent_scratch(wh_ctx* ctx, const std::string& slot, size_t bytes, void** dptr) {
   wh_ctx::Persist& e = ctx->persist[slot];
-  if (e.cap < bytes || !e.d) {
-    if (e.d) {
-      WH_CHECK(hipDeviceSynchronize());  // kernels of earlier calls may still use the buffer that is about to go
-      WH_CHECK(hipFree(e.d));
-      e.d = nullptr;
-    }
-    const size_t want = bytes < 256 ? 256 : bytes + bytes / 4;
-    WH_CHECK(hipMalloc(&e.d, want));
-    e.cap = want;
-  }
+  if (int rc = persist_grow(e, bytes)) return rc;
   *dptr = e.d;
   return 0;
 }

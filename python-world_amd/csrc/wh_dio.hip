@@ -478,13 +478,12 @@ extern "C" int wh_dio(wh_ctx* ctx, void* stream, const wh_batch* b, const double
     max_nf = std::max(max_nf, m.nf);
   }
   const int64_t F = b->total_frames;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t off = 0;
-  const size_t o_tmp = off; off += al(sizeof(double) * tmp_tot);
-  const size_t o_y = off; off += al(sizeof(double) * y_tot);
-  const size_t o_z = off; off += al(sizeof(double) * z_tot);
-  const size_t o_e = off; off += al(sizeof(double) * e_tot);
-  const size_t o_cnt = off; off += al(sizeof(int32_t) * (size_t)B * n_bands * 4);
+  wh::Carve carve;
+  const auto r_tmp = carve.take<double>(tmp_tot);
+  const auto r_y = carve.take<double>(y_tot);
+  const auto r_z = carve.take<double>(z_tot);
+  const auto r_e = carve.take<double>(e_tot);
+  const auto r_cnt = carve.take<int32_t>((int64_t)B * n_bands * 4);
   // segment-private event lists: 7 bands x B utterances alone cannot fill 256 CUs with their serial tile loops
   std::vector<int64_t> seg_cap(B), seg_off(B);
   int64_t se_tot = 0;
@@ -500,26 +499,19 @@ extern "C" int wh_dio(wh_ctx* ctx, void* stream, const wh_batch* b, const double
     seg_off[u] = se_tot;
     se_tot += (int64_t)n_bands * kBandSegs * 4 * seg_cap[u];
   }
-  const size_t o_se = off; off += al(sizeof(double) * se_tot);
-  const size_t o_scnt = off; off += al(sizeof(int32_t) * (size_t)B * n_bands * kBandSegs * 4);
-  const size_t o_raw = off; off += al(sizeof(double) * F * n_bands);
-  const size_t o_stab = off; off += al(sizeof(double) * F * n_bands);
-  const size_t o_sorted = off; off += al(sizeof(double) * F * n_bands);
-  const size_t o_work = off; off += al(sizeof(double) * (F * 5 + 8 * B));
-  if (int rc = wh::ws_reserve(ctx, off)) return rc;
-  char* ws = reinterpret_cast<char*>(ctx->ws);
+  const auto r_se = carve.take<double>(se_tot);
+  const auto r_scnt = carve.take<int32_t>((int64_t)B * n_bands * kBandSegs * 4);
+  const auto r_raw = carve.take<double>(F * n_bands);
+  const auto r_stab = carve.take<double>(F * n_bands);
+  const auto r_sorted = carve.take<double>(F * n_bands);
+  const auto r_work = carve.take<double>(F * 5 + 8 * B);
+  if (int rc = wh::ws_reserve(ctx, carve)) return rc;
+  void* ws = ctx->ws;
   DioUtt* d_meta = nullptr;
-  double* d_tmp = reinterpret_cast<double*>(ws + o_tmp);
-  double* d_y = reinterpret_cast<double*>(ws + o_y);
-  double* d_z = reinterpret_cast<double*>(ws + o_z);
-  double* d_e = reinterpret_cast<double*>(ws + o_e);
-  int32_t* d_cnt = reinterpret_cast<int32_t*>(ws + o_cnt);
-  double* d_se = reinterpret_cast<double*>(ws + o_se);
-  int32_t* d_scnt = reinterpret_cast<int32_t*>(ws + o_scnt);
-  double* d_raw = raw_out ? raw_out : reinterpret_cast<double*>(ws + o_raw);
-  double* d_stab = reinterpret_cast<double*>(ws + o_stab);
-  double* d_sorted = reinterpret_cast<double*>(ws + o_sorted);
-  double* d_work = reinterpret_cast<double*>(ws + o_work);
+  double *d_tmp = r_tmp.at(ws), *d_y = r_y.at(ws), *d_z = r_z.at(ws), *d_e = r_e.at(ws), *d_se = r_se.at(ws);
+  int32_t *d_cnt = r_cnt.at(ws), *d_scnt = r_scnt.at(ws);
+  double* d_raw = raw_out ? raw_out : r_raw.at(ws);
+  double *d_stab = r_stab.at(ws), *d_sorted = r_sorted.at(ws), *d_work = r_work.at(ws);
   double* d_taps = nullptr;
   double* d_lc = nullptr;
   double* d_bf = nullptr;

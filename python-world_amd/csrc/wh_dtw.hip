@@ -328,10 +328,14 @@ extern "C" int wh_dtw(wh_ctx* ctx, void* stream, const wh_batch* a, const wh_bat
   hipStream_t st = (hipStream_t)stream;
   int64_t* d_pairs = nullptr;
   if (int rc = wh::persistent_upload(ctx, st, "dtw.pairs", pairs, &d_pairs)) return rc;
-  void* scratch = nullptr;
-  if (int rc = wh::persistent_scratch(ctx, "dtw.scratch", (size_t)line_len * 8 + (size_t)bp_words * 4, &scratch)) return rc;
-  double* line = reinterpret_cast<double*>(scratch);
-  uint32_t* bp = reinterpret_cast<uint32_t*>(line + line_len);
+  wh::Carve carve;
+  const auto r_line = carve.take<double>(line_len);
+  const auto r_bp = carve.take<uint32_t>(bp_words);
+  if (!carve.ok()) return wh::fail_msg("wh_dtw", "scratch size beyond size_t");
+  char* scratch = nullptr;
+  if (int rc = wh::persistent_scratch(ctx, "dtw.scratch", carve.end(), &scratch)) return rc;
+  double* line = r_line.at(scratch);
+  uint32_t* bp = r_bp.at(scratch);
   const long long len_a = (a->total_frames - 1) * lda + d, len_b = (b->total_frames - 1) * ldb + d;
   const long long path_total = h_path_off[n];
   WH_LAUNCH(ctx, st, "dtw_recurrence_kernel", kDtwRecurrence[(d + 7) / 8 - 1], dim3((unsigned)n), dim3(WH_WAVE), 0,

@@ -391,9 +391,8 @@ extern "C" int wh_gmm_stats(wh_ctx* ctx, void* stream, const double* x, int64_t 
   const long long splits = gmm_splits(n_rows);
   if (splits > 65535) return wh::fail_msg("wh_gmm_stats", "too many rows for one call");
   const long long per = (long long)(d + 1) * (d + 1), len_p = splits * M * per;
-  void* scratch = nullptr;
-  if (int rc = wh::persistent_scratch(ctx, "gmm.partials", (size_t)len_p * sizeof(double), &scratch)) return rc;
-  double* part = reinterpret_cast<double*>(scratch);
+  double* part = nullptr;
+  if (int rc = wh::persistent_scratch(ctx, "gmm.partials", (size_t)len_p, &part)) return rc;
   WH_LAUNCH(ctx, st, "gmm_stats_kernel", gmm_stats_kernel, dim3((unsigned)M, (unsigned)splits),
             dim3(64 * kGmmStatsWaves), 0, x, n_rows, ldx, (n_rows - 1) * ldx + d, d, M, gamma, ldg,
             (n_rows - 1) * ldg + M, mu, part, len_p);

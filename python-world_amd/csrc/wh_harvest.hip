@@ -143,33 +143,39 @@ const char* plan_harvest(const wh_batch* b, double fs, double f0_floor, int deci
   return nullptr;
 }
 
-HvLayout layout_harvest(const HvPlan& p) {
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t B = p.B, nb = p.n_bands, f1 = p.f1_tot;
-  const size_t spec_bins = kOlsN / 2 + 1;
-  HvLayout l;
-  size_t off = 0;
-  l.o_tmp = off; off += al(sizeof(double) * p.t_tot);
-  l.o_y = off; off += al(sizeof(double) * p.y_tot);
-  l.o_z = off; off += al(sizeof(double) * p.z_tot);
-  l.o_mean = off; off += al(sizeof(double) * B * (1 + kMeanParts));  // means, then the partial sums
-  l.o_e = off; off += al(sizeof(double) * p.e_tot);
-  l.o_raw = off; off += p.need_map ? al(sizeof(double) * f1 * nb) : 0;
-  l.o_live = off; off += p.need_map ? al(sizeof(unsigned long long) * (size_t)p.l_tot) : 0;
-  l.o_hint = off; off += p.use_rawdet ? al(sizeof(int32_t) * 4 * (size_t)p.l_tot) : 0;
-  l.o_dc = off; off += al(sizeof(double) * f1 * kMaxC);
-  l.o_dn = off; off += al(sizeof(int32_t) * f1);
-  l.o_rf0 = off; off += al(sizeof(double) * f1 * kRows);
-  l.o_rsc = off; off += al(sizeof(double) * f1 * kRows);
-  l.o_keep = off; off += al(sizeof(uint32_t) * 4 * f1);
-  l.o_lst = off; off += al(sizeof(int64_t) * f1);
-  l.o_ct = off; off += al(contour_workspace_bytes(p.f1_tot, p.B));
+// THE layout of the Harvest workspace: reserves it and points `d` at its regions, in carve order.  raw / live hold nothing
+// without need_map, hint nothing without use_rawdet, the three spectra nothing without use_ols (a valid address all the same).
+int carve_harvest(wh_ctx* ctx, const HvPlan& p, HvDev& d) {
+  const int64_t B = p.B, nb = p.n_bands, f1 = p.f1_tot;
+  const int64_t spec_bins = kOlsN / 2 + 1;
+  wh::Carve c;
+  const auto tmp = c.take<double>(p.t_tot);
+  const auto y = c.take<double>(p.y_tot);
+  const auto z = c.take<double>(p.z_tot);
+  const auto mean = c.take<double>(B * (1 + kMeanParts));  // means, then the partial sums
+  const auto e = c.take<double>(p.e_tot);
+  const auto raw = c.take_if<double>(p.need_map, f1 * nb);
+  const auto live = c.take_if<unsigned long long>(p.need_map, p.l_tot);
+  const auto hint = c.take_if<int32_t>(p.use_rawdet, 4 * p.l_tot);
+  const auto dc = c.take<double>(f1 * kMaxC);
+  const auto dn = c.take<int32_t>(f1);
+  const auto rf0 = c.take<double>(f1 * kRows);
+  const auto rsc = c.take<double>(f1 * kRows);
+  const auto keep = c.take<uint32_t>(4 * f1);
+  const auto lst = c.take<int64_t>(f1);
+  const auto ct = wh::hv_carve_contour(c, p);
   // overlap-save band filters: the channels' tap spectra, the tile spectra of every utterance, the real (zero-phase) tap spectra
-  l.o_tspec = off; off += p.use_ols ? al(sizeof(double2) * spec_bins * nb) : 0;
-  l.o_zspec = off; off += p.use_ols ? al(sizeof(double2) * spec_bins * (size_t)p.tile_off[p.B]) : 0;
-  l.o_tre = off; off += p.use_ols ? al(sizeof(double) * spec_bins * nb) : 0;
-  l.total = off;
-  return l;
+  const auto tspec = c.take_if<double2>(p.use_ols, spec_bins * nb);
+  const auto zspec = c.take_if<double2>(p.use_ols, spec_bins * p.tile_off[p.B]);
+  const auto tre = c.take_if<double>(p.use_ols, spec_bins * nb);
+  if (int rc = wh::ws_reserve(ctx, c)) return rc;
+  void* ws = ctx->ws;
+  d.tmp = tmp.at(ws); d.y = y.at(ws); d.z = z.at(ws); d.mean = mean.at(ws); d.e = e.at(ws);
+  d.raw = raw.at(ws); d.live = live.at(ws); d.hint = hint.at(ws);
+  d.dc = dc.at(ws); d.dn = dn.at(ws); d.rf0 = rf0.at(ws); d.rsc = rsc.at(ws); d.keep = keep.at(ws); d.lst = lst.at(ws);
+  d.ct = ct.at(ws);
+  d.tspec = tspec.at(ws); d.zspec = zspec.at(ws); d.tre = tre.at(ws);
+  return 0;
 }
 
 }  // namespace
@@ -193,32 +199,10 @@ extern "C" int wh_harvest(wh_ctx* ctx, void* stream, const wh_batch* b, const do
     return wh::fail_msg("wh_harvest", err);
   }
   ctx->hv_caps_next.clear();  // explicit capacities serve one call
-  const HvLayout l = layout_harvest(p);
-  if (int rc = wh::ws_reserve(ctx, l.total)) return rc;
-  char* ws = reinterpret_cast<char*>(ctx->ws);
   HvDev d;
-  d.tmp = reinterpret_cast<double*>(ws + l.o_tmp);
-  d.y = reinterpret_cast<double*>(ws + l.o_y);
-  d.z = reinterpret_cast<double*>(ws + l.o_z);
-  d.mean = reinterpret_cast<double*>(ws + l.o_mean);
-  d.e = reinterpret_cast<double*>(ws + l.o_e);
-  d.raw = reinterpret_cast<double*>(ws + l.o_raw);
-  d.live = reinterpret_cast<unsigned long long*>(ws + l.o_live);
-  d.hint = reinterpret_cast<int32_t*>(ws + l.o_hint);
-  d.dc = reinterpret_cast<double*>(ws + l.o_dc);
-  d.dn = reinterpret_cast<int32_t*>(ws + l.o_dn);
-  d.rf0 = reinterpret_cast<double*>(ws + l.o_rf0);
-  d.rsc = reinterpret_cast<double*>(ws + l.o_rsc);
-  d.keep = reinterpret_cast<uint32_t*>(ws + l.o_keep);
-  d.lst = reinterpret_cast<int64_t*>(ws + l.o_lst);
-  d.ct = ws + l.o_ct;
-  d.tspec = reinterpret_cast<double2*>(ws + l.o_tspec);
-  d.zspec = reinterpret_cast<double2*>(ws + l.o_zspec);
-  d.tre = reinterpret_cast<double*>(ws + l.o_tre);
+  if (int rc = carve_harvest(ctx, p, d)) return rc;
   {  // the lists' counts: a buffer of their own (wh_harvest_event_counts reads them after later stages have used the scratch)
-    void* cnt = nullptr;
-    if (int rc = wh::persistent_scratch(ctx, "hv.counts", sizeof(int32_t) * (size_t)p.B * n_bands * 4, &cnt)) return rc;
-    d.cnt = reinterpret_cast<int32_t*>(cnt);
+    if (int rc = wh::persistent_scratch(ctx, "hv.counts", (size_t)p.B * n_bands * 4, &d.cnt)) return rc;
     ctx->hv_last_cnt = d.cnt;
     ctx->hv_last_cnt_lists = (int64_t)p.B * n_bands;
   }

@@ -12,6 +12,11 @@
 #include <vector>
 
 #include "../../include/world_hip.h"
+#include "wh_arena.h"
+
+namespace wh {
+struct PulseRec;  // wh_syn_types.h
+}
 
 struct wh_ctx {
   int device = 0;
@@ -47,8 +52,12 @@ struct wh_ctx {
     bool valid = false;
     int n_utt = 0;
     int64_t pulse_cap = 0, ny_tot = 0, frames = 0;
-    size_t o_vuv = 0, o_pt = 0, o_pi = 0, o_ps = 0, o_pn = 0, o_pc = 0, o_pb = 0, o_rec = 0;
-    size_t o_phase = 0;
+    // the regions of the workspace it publishes (wh::TimeBaseLayout, then the pulse bases and records)
+    wh::Region<double> phase, pt, ps;
+    wh::Region<uint8_t> vuv;
+    wh::Region<int64_t> pi, pn, pb;
+    wh::Region<int32_t> pc;
+    wh::Region<wh::PulseRec> rec;
     std::vector<int64_t> f_off;  // first frame of every utterance (wh_synthesis_timebase_read makes the rows relative)
   } timebase;
   // Harvest's zero-crossing lists (wh_harvest_set_event_caps / wh_harvest_event_counts): the capacities the NEXT
@@ -86,6 +95,7 @@ int fail(const char* where, hipError_t e);
 inline void clear_runtime_error() { (void)hipGetLastError(); }  // (the runtime's sticky "last error": read is cleared)
 int fail_msg(const char* where, const char* msg);
 int ws_reserve(wh_ctx* ctx, size_t bytes);  // grows ctx->ws (hipFree + hipMalloc => implicit sync)
+int ws_reserve(wh_ctx* ctx, const Carve& layout);  // layout.end() bytes; an error if the layout is not ok()
 inline const double2* twiddle(const wh_ctx* ctx, int n) { return ctx->d_twiddle + n; }
 // Upload-once constant table keyed by name (synchronous on first use, cached afterwards).
 int const_table(wh_ctx* ctx, const std::string& key, const std::vector<double>& host, const double** out);
@@ -113,6 +123,13 @@ template <typename T>
 inline int persistent_upload(wh_ctx* ctx, hipStream_t st, const std::string& slot, const std::vector<T>& v, T** dptr) {
   void* p = nullptr;
   const int rc = persistent_upload(ctx, st, slot, v.data(), v.size() * sizeof(T), &p);
+  *dptr = reinterpret_cast<T*>(p);
+  return rc;
+}
+template <typename T>
+inline int persistent_scratch(wh_ctx* ctx, const std::string& slot, size_t count, T** dptr) {
+  void* p = nullptr;
+  const int rc = persistent_scratch(ctx, slot, count * sizeof(T), &p);
   *dptr = reinterpret_cast<T*>(p);
   return rc;
 }

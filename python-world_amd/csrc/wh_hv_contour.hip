@@ -586,10 +586,43 @@ __global__ __launch_bounds__(256) void hc_pick_kernel(const HvUtt* __restrict__ 
 
 namespace wh {
 
-size_t contour_workspace_bytes(int64_t f1_tot, int n_utt) {
-  // rows + runs + sections + channels, generously aligned
-  return (size_t)f1_tot * 6 * 8 + (size_t)(f1_tot + 16 * n_utt) * 2 * 4 + (size_t)(f1_tot / 2 + 16 * n_utt) * sizeof(HcSec) +
-         (size_t)(f1_tot * 32 + 1024 * n_utt) * 8 + sizeof(HcUtt) * n_utt + 4096;
+namespace {
+// THE layout of the contour back end's share, relative to the share's start, and the per-utterance slices inside it.
+struct HcLayout {
+  std::vector<HcUtt> hc;
+  int64_t max_secs = 0;
+  Carve c;
+  Region<double> rows, ch;
+  Region<int32_t> runs, ns;
+  Region<HcSec> secs;
+  explicit HcLayout(const HvPlan& p) : hc(p.B) {
+    int64_t run_tot = 0, sec_tot = 0, ch_tot = 0;
+    for (int u = 0; u < p.B; ++u) {
+      HcUtt& h = hc[u];
+      const int64_t nf1 = p.meta[u].nf1;
+      h.f_base = p.meta[u].f1_off * 6;
+      h.rcap = nf1 / 2 + 8;
+      h.run_base = run_tot;
+      run_tot += 2 * h.rcap;
+      h.sec_base = sec_tot;
+      sec_tot += h.rcap;
+      h.ch_base = ch_tot;
+      h.ch_cap = nf1 * 32 + 1024;
+      ch_tot += h.ch_cap;
+      max_secs = std::max(max_secs, nf1 / 7 + 2);
+    }
+    rows = c.take<double>(p.f1_tot * 6);
+    runs = c.take<int32_t>(run_tot);
+    secs = c.take<HcSec>(sec_tot);
+    ns = c.take<int32_t>(p.B);
+    ch = c.take<double>(ch_tot);
+  }
+};
+}  // namespace
+
+Region<char> hv_carve_contour(Carve& c, const HvPlan& p) {
+  const HcLayout l(p);
+  return c.take<char>(l.c.ok() ? (int64_t)l.c.end() : -1);
 }
 
 int hv_launch_contour(wh_ctx* ctx, hipStream_t st, const HvPlan& p, const HvDev& d, const double* tp, double* f0_out,
@@ -597,40 +630,16 @@ int hv_launch_contour(wh_ctx* ctx, hipStream_t st, const HvPlan& p, const HvDev&
   const int B = p.B;
   const std::vector<HvUtt>& meta = p.meta;
   const HvUtt* d_meta = d.meta;
-  const int64_t f1_tot = p.f1_tot, max_nf1 = p.max_nf1, max_nf = p.max_nf;
+  const int64_t max_nf1 = p.max_nf1, max_nf = p.max_nf;
   const double *d_pf0 = d.rf0, *d_psc = d.rsc;
   const int64_t* d_lst = d.lst;
   const uint32_t* d_keep = d.keep;
-  char* d_ws = d.ct;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  std::vector<HcUtt> hc(B);
-  int64_t run_tot = 0, sec_tot = 0, ch_tot = 0, max_secs = 0;
-  for (int u = 0; u < B; ++u) {
-    HcUtt& h = hc[u];
-    h.f_base = meta[u].f1_off * 6;
-    h.rcap = meta[u].nf1 / 2 + 8;
-    h.run_base = run_tot;
-    run_tot += 2 * h.rcap;
-    h.sec_base = sec_tot;
-    sec_tot += h.rcap;
-    h.ch_base = ch_tot;
-    h.ch_cap = meta[u].nf1 * 32 + 1024;
-    ch_tot += h.ch_cap;
-    max_secs = std::max(max_secs, meta[u].nf1 / 7 + 2);
-  }
-  size_t off = 0;
-  const size_t o_rows = off; off += al(sizeof(double) * f1_tot * 6);
-  const size_t o_runs = off; off += al(sizeof(int32_t) * run_tot);
-  const size_t o_secs = off; off += al(sizeof(HcSec) * sec_tot);
-  const size_t o_ns = off; off += al(sizeof(int32_t) * B);
-  const size_t o_ch = off; off += al(sizeof(double) * ch_tot);
-  (void)off;
+  const HcLayout l(p);
+  const std::vector<HcUtt>& hc = l.hc;
   HcUtt* d_hc = nullptr;
-  double* d_rows = reinterpret_cast<double*>(d_ws + o_rows);
-  int32_t* d_runs = reinterpret_cast<int32_t*>(d_ws + o_runs);
-  HcSec* d_secs = reinterpret_cast<HcSec*>(d_ws + o_secs);
-  int32_t* d_ns = reinterpret_cast<int32_t*>(d_ws + o_ns);
-  double* d_ch = reinterpret_cast<double*>(d_ws + o_ch);
+  double *d_rows = l.rows.at(d.ct), *d_ch = l.ch.at(d.ct);
+  int32_t *d_runs = l.runs.at(d.ct), *d_ns = l.ns.at(d.ct);
+  HcSec* d_secs = l.secs.at(d.ct);
   if (int rc = persistent_upload(ctx, st, "hv.contour", hc, &d_hc)) return rc;
   const dim3 gf((unsigned)((max_nf1 + 255) / 256), B);
   WH_LAUNCH(ctx, st, "hc_base_kernel", hc_base_kernel, gf, dim3(256), 0, d_meta, d_hc, d_pf0, d_psc, d_lst, d_keep,
@@ -638,7 +647,7 @@ int hv_launch_contour(wh_ctx* ctx, hipStream_t st, const HvPlan& p, const HvDev&
   WH_LAUNCH(ctx, st, "hc_step1_kernel", hc_step1_kernel, gf, dim3(256), 0, d_meta, d_hc, d_rows);
   WH_LAUNCH(ctx, st, "hc_sections_kernel", hc_sections_kernel, dim3(B), dim3(256), 0, d_meta, d_hc, d_rows, d_runs,
             d_secs, d_ns);
-  WH_LAUNCH(ctx, st, "hc_extend_kernel", hc_extend_kernel, dim3((unsigned)max_secs, B), dim3(64), 0, d_meta, d_hc,
+  WH_LAUNCH(ctx, st, "hc_extend_kernel", hc_extend_kernel, dim3((unsigned)l.max_secs, B), dim3(64), 0, d_meta, d_hc,
             d_rows, d_pf0, d_lst, d_keep, d_secs, d_ns, d_ch);
   WH_LAUNCH(ctx, st, "hc_merge_kernel", hc_merge_kernel, dim3(B), dim3(256), 0, d_meta, d_hc, d_rows, d_pf0, d_psc,
             d_lst, d_keep, d_secs, d_ns, d_ch, d_runs);

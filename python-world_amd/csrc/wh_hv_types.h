@@ -1,6 +1,6 @@
 // What the Harvest units share (wh_harvest.hip, wh_hv_front.hip, wh_hv_refine.hip, wh_hv_contour.hip): the
-// per-utterance record, the constants of the candidate map, the plan of one call, the one definition of its workspace
-// layout, and the stage launchers that cross unit boundaries.  Include after wh_host.h.
+// per-utterance record, the constants of the candidate map, the plan of one call, its device
+// pointers, and the stage launchers that cross unit boundaries.  Include after wh_host.h.
 #pragma once
 #include <vector>
 
@@ -59,14 +59,7 @@ struct HvPlan {
   bool need_map = false;    // the [channel][frame] candidate map and its bit map exist (the pair, or the debug read-out)
 };
 
-// Byte offsets of the Harvest workspace, each region rounded up to 256 bytes, in carve order.  o_raw / o_live hold nothing
-// without need_map, o_hint nothing without use_rawdet, the three spectra nothing without use_ols.
-struct HvLayout {
-  size_t o_tmp, o_y, o_z, o_mean, o_e, o_raw, o_live, o_hint, o_dc, o_dn, o_rf0, o_rsc, o_keep, o_lst, o_ct;
-  size_t o_tspec, o_zspec, o_tre, total;
-};
-
-// Device pointers of one call: the workspace regions and the persistent uploads.
+// Device pointers of one call: the workspace regions (wh_harvest.hip: carve_harvest) and the persistent uploads.
 struct HvDev {
   HvUtt* meta = nullptr;
   BandJob* jobs = nullptr;
@@ -98,7 +91,8 @@ int hv_launch_raw_detect(wh_ctx* ctx, hipStream_t st, const HvPlan& p, double f0
 int hv_launch_refine(wh_ctx* ctx, hipStream_t st, const HvPlan& p, double f0_floor, double f0_ceil, const HvDev& d);
 int hv_launch_prune(wh_ctx* ctx, hipStream_t st, const HvPlan& p, const HvDev& d);
 // wh_hv_contour.hip
-size_t contour_workspace_bytes(int64_t f1_tot, int n_utt);
+// the contour back end's share of the Harvest workspace, taken from `c`: exactly what hv_launch_contour carves from it
+Region<char> hv_carve_contour(Carve& c, const HvPlan& p);
 int hv_launch_contour(wh_ctx* ctx, hipStream_t st, const HvPlan& p, const HvDev& d, const double* tp, double* f0_out,
                       double* vuv_out, double* dbg_f0_1ms);
 

@@ -285,10 +285,9 @@ extern "C" int wh_mlpg(wh_ctx* ctx, void* stream, const wh_batch* b, const doubl
   hipStream_t st = (hipStream_t)stream;
   const int B = 2 * half;
   const long long len_l = frames * B * d;
-  void* scratch = nullptr;
+  double* mult = nullptr;
   if (B > 0)
-    if (int rc = wh::persistent_scratch(ctx, "mlpg.scratch", (size_t)len_l * sizeof(double), &scratch)) return rc;
-  double* mult = reinterpret_cast<double*>(scratch);
+    if (int rc = wh::persistent_scratch(ctx, "mlpg.scratch", (size_t)len_l, &mult)) return rc;
   const long long len_m = (frames - 1) * ldm + width, len_v = ldv ? (frames - 1) * ldv + width : width;
   const long long len_o = (frames - 1) * ldo + d;
   WH_LAUNCH(ctx, st, "mlpg_kernel", B == 0 ? mlpg_kernel<0> : B == 2 ? mlpg_kernel<2> : mlpg_kernel<4>,

@@ -307,10 +307,9 @@ extern "C" int wh_regrid_rows(wh_ctx* ctx, void* stream, const wh_batch* src, co
     if (a0 < b1 && b0 < a1) return wh::fail_msg("wh_regrid_rows", "out must not overlap in");
   }
   hipStream_t st = (hipStream_t)stream;
-  void* plan = nullptr;
-  if (int rc = wh::persistent_scratch(ctx, "regrid.plan", (size_t)n_dst * 32, &plan)) return rc;
-  long long* pj = reinterpret_cast<long long*>(plan);
-  double* pdx = reinterpret_cast<double*>(plan) + n_dst;
+  long long* pj = nullptr;  // per frame: the source row, then three doubles
+  if (int rc = wh::persistent_scratch(ctx, "regrid.plan", (size_t)n_dst * 4, &pj)) return rc;
+  double* pdx = reinterpret_cast<double*>(pj + n_dst);
   double* pden = pdx + n_dst;
   double* pdx2 = pden + n_dst;
   const long long pblocks = (n_dst + 255) / 256;

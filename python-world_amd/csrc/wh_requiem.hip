@@ -369,27 +369,23 @@ extern "C" int wh_synthesis_requiem(wh_ctx* ctx, void* stream, const wh_batch* b
     rq[u].row_off = rows_tot;
     rows_tot += rq[u].n_runs * ((runf - 1) * rq[u].hop + fft_size + 1);
   }
-  const wh::TimeBaseLayout lay(B, ny_tot, pulse_cap, max_ny);
-  auto al = lay.al;
-  size_t off = lay.end;
-  const size_t o_lin = off; off += al(sizeof(double) * F * n_bands);
-  const size_t o_exc = off; off += al(sizeof(double) * ny_tot);
-  const size_t o_pw = off; off += al(sizeof(double) * B * pulse_cap * n_bands);  // band weights per pulse (the gains reuse o_pt)
-  const size_t o_rows = off; off += al(sizeof(double) * (size_t)(rows_tot + 8));
-  if (int rc = wh::ws_reserve(ctx, off)) return rc;
-  char* ws = reinterpret_cast<char*>(ctx->ws);
+  wh::Carve carve;
+  const wh::TimeBaseLayout lay(carve, B, ny_tot, pulse_cap, max_ny);
+  const auto r_lin = carve.take<double>(F * n_bands);
+  const auto r_exc = carve.take<double>(ny_tot);
+  const auto r_pw = carve.take<double>(B * pulse_cap * n_bands);  // band weights per pulse (the gains reuse lay.pt)
+  const auto r_rows = carve.take<double>(rows_tot + 8);
+  if (int rc = wh::ws_reserve(ctx, carve)) return rc;
+  void* ws = ctx->ws;
   SynUtt* d_meta = nullptr;
   ReqUtt* d_rq = nullptr;
-  double* d_pt = reinterpret_cast<double*>(ws + lay.o_pt);  // (pulse times; then the pulse gains)
-  const uint8_t* d_vuv = reinterpret_cast<const uint8_t*>(ws + lay.o_vuv);
-  const int64_t* d_pi = reinterpret_cast<const int64_t*>(ws + lay.o_pi);
-  const int32_t* d_pc = reinterpret_cast<const int32_t*>(ws + lay.o_pc);
-  double* d_lin = reinterpret_cast<double*>(ws + o_lin);
-  double* d_exc = reinterpret_cast<double*>(ws + o_exc);
-  double* d_pw = reinterpret_cast<double*>(ws + o_pw);
+  double* d_pt = lay.pt.at(ws);  // (pulse times; then the pulse gains)
+  const uint8_t* d_vuv = lay.vuv.at(ws);
+  const int64_t* d_pi = lay.pi.at(ws);
+  const int32_t* d_pc = lay.pc.at(ws);
+  double *d_lin = r_lin.at(ws), *d_exc = r_exc.at(ws), *d_pw = r_pw.at(ws), *d_rows = r_rows.at(ws);
   if (int rc = wh::persistent_upload(ctx, st, "syn.meta", meta, &d_meta)) return rc;
   if (int rc = wh::persistent_upload(ctx, st, "syn.req", rq, &d_rq)) return rc;
-  double* d_rows = reinterpret_cast<double*>(ws + o_rows);
   if (int rc = wh::launch_pulses(ctx, st, B, max_ny, d_meta, tp, f0, vuv, fs, 0.0, h_y_off, ws, lay)) return rc;
   WH_LAUNCH(ctx, st, "req_linap_kernel", req_linap_kernel, dim3((unsigned)((F * n_bands + 255) / 256)), dim3(256), 0,
             band_aperiodicity, F * n_bands, d_lin);

@@ -163,18 +163,14 @@ extern "C" int wh_requiem_seeds(wh_ctx* ctx, void* stream, double fs, int fft_si
   for (int i = 0; i < 3; ++i) lens[i] = (int)(8 * (base[i] * fs / 48000 + 0.5));
   if (lens[0] < 4 || lens[2] > 1024) return wh::fail_msg("wh_requiem_seeds", "sampling rate outside the supported range");
   const int max_seg = n / lens[0] + 2;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t off = 0;
-  const size_t o_vel = off; off += al(sizeof(double) * n);
-  const size_t o_ss = off; off += al(sizeof(int32_t) * max_seg);
-  const size_t o_sl = off; off += al(sizeof(int32_t) * max_seg);
-  const size_t o_ns = off; off += 256;
-  if (int rc = wh::ws_reserve(ctx, off)) return rc;
-  char* ws = reinterpret_cast<char*>(ctx->ws);
-  double* d_vel = reinterpret_cast<double*>(ws + o_vel);
-  int32_t* d_ss = reinterpret_cast<int32_t*>(ws + o_ss);
-  int32_t* d_sl = reinterpret_cast<int32_t*>(ws + o_sl);
-  int32_t* d_ns = reinterpret_cast<int32_t*>(ws + o_ns);
+  wh::Carve carve;
+  const auto r_vel = carve.take<double>(n);
+  const auto r_ss = carve.take<int32_t>(max_seg);
+  const auto r_sl = carve.take<int32_t>(max_seg);
+  const auto r_ns = carve.take<int32_t>(1);
+  if (int rc = wh::ws_reserve(ctx, carve)) return rc;
+  double* d_vel = r_vel.at(ctx->ws);
+  int32_t *d_ss = r_ss.at(ctx->ws), *d_sl = r_sl.at(ctx->ws), *d_ns = r_ns.at(ctx->ws);
   WH_CHECK(hipMemsetAsync(d_vel, 0, sizeof(double) * n, st));
   WH_LAUNCH(ctx, st, "velvet_layout_kernel", velvet_layout_kernel, dim3(1), dim3(64), 0, n, lens[0], lens[1], lens[2],
             seed, max_seg, d_ss, d_sl, d_ns);

@@ -227,19 +227,14 @@ extern "C" int wh_swipe(wh_ctx* ctx, void* stream, const wh_batch* b, const doub
     max_l = std::max(max_l, (size_t)seg * n_erb);
     max_si = std::max(max_si, (size_t)seg * w.n_c);
   }
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t off = 0;
-  const size_t o_s = off; off += al(sizeof(double) * (size_t)b->total_frames * n_cand);
-  const size_t o_mag = off; off += al(sizeof(double) * max_mag);
-  const size_t o_l = off; off += al(sizeof(double) * max_l);
-  const size_t o_si = off; off += al(sizeof(double) * max_si);
-  if (int rc = wh::ws_reserve(ctx, off)) return rc;
-  char* ws = reinterpret_cast<char*>(ctx->ws);
-  double* d_S = reinterpret_cast<double*>(ws + o_s);
-  double* d_mag = reinterpret_cast<double*>(ws + o_mag);
-  double* d_L = reinterpret_cast<double*>(ws + o_l);
-  double* d_si = reinterpret_cast<double*>(ws + o_si);
-  WH_CHECK(hipMemsetAsync(d_S, 0, sizeof(double) * (size_t)b->total_frames * n_cand, st));
+  wh::Carve carve;
+  const auto r_S = carve.take<double>(b->total_frames * n_cand);
+  const auto r_mag = carve.take<double>((int64_t)max_mag);
+  const auto r_L = carve.take<double>((int64_t)max_l);
+  const auto r_si = carve.take<double>((int64_t)max_si);
+  if (int rc = wh::ws_reserve(ctx, carve)) return rc;
+  double *d_S = r_S.at(ctx->ws), *d_mag = r_mag.at(ctx->ws), *d_L = r_L.at(ctx->ws), *d_si = r_si.at(ctx->ws);
+  WH_CHECK(hipMemsetAsync(d_S, 0, r_S.bytes(), st));
   int64_t max_nf = 0;
   for (int u = 0; u < B; ++u) max_nf = std::max(max_nf, b->h_frame_off[u + 1] - b->h_frame_off[u]);
   for (int i = 0; i < n_win; ++i) {

@@ -107,27 +107,16 @@ __device__ __forceinline__ int first_pulse_at(const int64_t* __restrict__ pi, in
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 // (wh::dispatch_fft_size, the switch over the kernels' transform lengths: wh_host.h)
-// scratch of the pulse stage: crossing masks (one byte per 4 samples) and per-tile counts (wh_timebase.hip: launch_pulses)
-size_t pulse_scratch_bytes(int B, int64_t max_ny);
-
-// The front of every synthesis workspace: phase increments / cumulative phase, per-sample voicing, then per pulse slot the
-// time, 1-based index, fractional shift and noise offset, the pulse counts and the pulse stage's scratch — each rounded
-// up to 256 bytes.  `end`: where a caller's own buffers may follow.
+// The front of every synthesis workspace, taken from `c` (the caller's own regions follow from the same carve): phase
+// increments / cumulative phase, per-sample voicing, then per pulse slot the time, 1-based index, fractional shift and
+// noise offset, the pulse counts and the pulse stage's scratch — crossing masks (one byte per 4 samples) and per-tile
+// counts (wh_timebase.hip: launch_pulses).
 struct TimeBaseLayout {
-  size_t o_phase, o_vuv, o_pt, o_pi, o_ps, o_pn, o_pc, o_px, end;
-  static size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-  TimeBaseLayout(int B, int64_t ny_tot, int64_t pulse_cap, int64_t max_ny) {
-    size_t off = 0;
-    o_phase = off; off += al(sizeof(double) * ny_tot);
-    o_vuv = off; off += al((size_t)ny_tot);
-    o_pt = off; off += al(sizeof(double) * B * pulse_cap);
-    o_pi = off; off += al(sizeof(int64_t) * B * pulse_cap);
-    o_ps = off; off += al(sizeof(double) * B * pulse_cap);
-    o_pn = off; off += al(sizeof(int64_t) * B * pulse_cap);
-    o_pc = off; off += al(sizeof(int32_t) * B);
-    o_px = off; off += pulse_scratch_bytes(B, max_ny);
-    end = off;
-  }
+  Region<double> phase, pt, ps;
+  Region<int64_t> pi, pn;
+  Region<int32_t> pc, tile_cnt;
+  Region<uint8_t> vuv, masks;
+  TimeBaseLayout(Carve& c, int B, int64_t ny_tot, int64_t pulse_cap, int64_t max_ny);
 };
 
 // meta[u] of every utterance of the batch (noise == nullptr: no host noise stream) and the longest output.
@@ -138,7 +127,7 @@ int fill_syn_meta(const char* who, const wh_batch* b, const int64_t* h_y_off, co
 int exact_cumsum_segments(wh_ctx* ctx, hipStream_t st, double* d_data, const int64_t* h_off, int n_seg);
 // prep_kernel, the exact phase scan and the pulse kernels into the buffers of `lay` in the workspace `ws`.
 int launch_pulses(wh_ctx* ctx, hipStream_t st, int B, int64_t max_ny, const SynUtt* d_meta, const double* tp,
-                  const double* f0, const double* vuv, double fs, double f0_low_limit, const int64_t* h_y_off, char* ws,
+                  const double* f0, const double* vuv, double fs, double f0_low_limit, const int64_t* h_y_off, void* ws,
                   const TimeBaseLayout& lay);
 
 }  // namespace wh

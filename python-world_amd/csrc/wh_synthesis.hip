@@ -341,25 +341,22 @@ int launch_resp(wh_ctx* ctx, hipStream_t st, const RespCall& c) {
   for (int u = 0; u < B; ++u) row_base[u + 1] = row_base[u] + per_sample * h_ny[u] + 4 * (N + 1);
   int64_t* d_row_base = nullptr;
   if (int rc = wh::persistent_upload(ctx, st, "syn.row_base", row_base, &d_row_base)) return rc;
-  void* d_rows = nullptr;
-  void* d_rb = nullptr;
-  void* d_ro = nullptr;
-  if (int rc = wh::persistent_scratch(ctx, "syn.ola_rows", sizeof(double) * (size_t)row_base[B], &d_rows)) return rc;
-  if (int rc = wh::persistent_scratch(ctx, "syn.run_base", sizeof(int64_t) * ((size_t)B + 1), &d_rb)) return rc;
-  if (int rc = wh::persistent_scratch(ctx, "syn.row_off", sizeof(int64_t) * (size_t)runs_cap * B, &d_ro)) return rc;
-  WH_LAUNCH(ctx, st, "pulse_run_base_kernel", pulse_run_base_kernel, dim3(1), dim3(64), 0, p_count, B, resp_run(N),
-            reinterpret_cast<int64_t*>(d_rb));
+  double* d_rows = nullptr;
+  int64_t *d_rb = nullptr, *d_ro = nullptr;
+  if (int rc = wh::persistent_scratch(ctx, "syn.ola_rows", (size_t)row_base[B], &d_rows)) return rc;
+  if (int rc = wh::persistent_scratch(ctx, "syn.run_base", (size_t)B + 1, &d_rb)) return rc;
+  if (int rc = wh::persistent_scratch(ctx, "syn.row_off", (size_t)runs_cap * B, &d_ro)) return rc;
+  WH_LAUNCH(ctx, st, "pulse_run_base_kernel", pulse_run_base_kernel, dim3(1), dim3(64), 0, p_count, B, resp_run(N), d_rb);
   WH_LAUNCH(ctx, st, "pulse_rows_kernel", pulse_rows_kernel<N>, dim3(B), dim3(256), 0, d_meta, p_idx, p_count, runs_cap,
-            d_row_base, reinterpret_cast<int64_t*>(d_ro), ctx->d_flags);
+            d_row_base, d_ro, ctx->d_flags);
   // one workgroup per run of resp_run(N) pulse slots; runs past the real pulse count exit at once
   const int64_t grid = wh::xcd_grid(runs_cap * B);
   const RespArgs ra{d_meta, c.tp, c.spec, c.ap, c.fs, c.p_rec, c.p_base, B, c.noise, c.seed, d_dc, ctx->d_twiddle, d_mt,
-                    reinterpret_cast<double*>(d_rows), d_row_base, reinterpret_cast<const int64_t*>(d_rb),
-                    reinterpret_cast<const int64_t*>(d_ro), runs_cap};
+                    d_rows, d_row_base, d_rb, d_ro, runs_cap};
   WH_LAUNCH(ctx, st, "response_kernel", response_kernel<N>, dim3((unsigned)grid), dim3(ft_syn(N)), lds, ra);
   WH_LAUNCH(ctx, st, "response_gather_kernel", response_gather_kernel<N>,
             dim3((unsigned)((max_ny + kGatherTile - 1) / kGatherTile), B), dim3(256), 0, d_meta, p_idx, p_count,
-            reinterpret_cast<const double*>(d_rows), d_row_base, reinterpret_cast<const int64_t*>(d_ro), runs_cap, c.y);
+            d_rows, d_row_base, d_ro, runs_cap, c.y);
   return 0;
 }
 
@@ -386,13 +383,13 @@ extern "C" int wh_synthesis_render(wh_ctx* ctx, void* stream, const wh_batch* b,
   std::vector<SynUtt> meta;
   int64_t max_ny = 0;
   if (int rc = wh::fill_syn_meta("wh_synthesis_render", b, h_y_off, h_t0, h_dt, pulse_cap, noise, h_noise_off, meta, &max_ny)) return rc;
-  const char* ws = reinterpret_cast<const char*>(timebase_ctx->ws);
+  const void* ws = timebase_ctx->ws;
   SynUtt* d_meta = nullptr;
   if (int rc = wh::persistent_upload(ctx, st, "syn.meta", meta, &d_meta)) return rc;
-  const int64_t* d_pb = reinterpret_cast<const int64_t*>(ws + t.o_pb);
-  const int64_t* d_pi = reinterpret_cast<const int64_t*>(ws + t.o_pi);
-  const PulseRec* d_rec = reinterpret_cast<const PulseRec*>(ws + t.o_rec);
-  const int32_t* d_pc = reinterpret_cast<const int32_t*>(ws + t.o_pc);
+  const int64_t* d_pb = t.pb.at(ws);
+  const int64_t* d_pi = t.pi.at(ws);
+  const PulseRec* d_rec = t.rec.at(ws);
+  const int32_t* d_pc = t.pc.at(ws);
   if (noise)  // (the time base knows nothing about the noise stream: the cover test belongs to the call that is given one)
     WH_LAUNCH(ctx, st, "noise_cover_kernel", noise_cover_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, d_meta,
               d_rec, d_pb, B, ctx->d_flags);

@@ -433,11 +433,14 @@ int wh::exact_cumsum_segments(wh_ctx* ctx, hipStream_t st, double* d_data, const
   int64_t *d_lp = nullptr, *d_tb = nullptr;
   if (int rc = wh::persistent_upload(ctx, st, "cumsum.long", l_pairs, &d_lp)) return rc;
   if (int rc = wh::persistent_upload(ctx, st, "cumsum.tiles", tb, &d_tb)) return rc;
-  void* d_scr = nullptr;  // per tile: S / A, C (doubles) and the tile record
-  if (int rc = wh::persistent_scratch(ctx, "cumsum.scratch", (size_t)nt * (2 * sizeof(double) + sizeof(XsTile)), &d_scr)) return rc;
-  double* d_S = reinterpret_cast<double*>(d_scr);
-  double* d_C = d_S + nt;
-  XsTile* d_tiles = reinterpret_cast<XsTile*>(d_C + nt);
+  wh::Carve c;  // per tile: S / A, C (doubles) and the tile record
+  const auto r_S = c.take<double>(nt), r_C = c.take<double>(nt);
+  const auto r_tiles = c.take<XsTile>(nt);
+  if (!c.ok()) return wh::fail_msg("exact_cumsum_segments", "scratch size beyond size_t");
+  char* d_scr = nullptr;
+  if (int rc = wh::persistent_scratch(ctx, "cumsum.scratch", c.end(), &d_scr)) return rc;
+  double *d_S = r_S.at(d_scr), *d_C = r_C.at(d_scr);
+  XsTile* d_tiles = r_tiles.at(d_scr);
   WH_LAUNCH(ctx, st, "xs_tile_sum_kernel", xs_tile_sum_kernel, dim3((unsigned)nt), dim3(256), 0, d_data, d_lp, d_tb, ns,
             d_S);
   WH_LAUNCH(ctx, st, "xs_prefix_kernel", xs_prefix_kernel, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, d_tb, ns,
@@ -657,27 +660,30 @@ __global__ __launch_bounds__(256) void pulse_frames_kernel(const SynUtt* __restr
 inline int pulse_tiles(int64_t max_ny) { return max_ny > 1 ? (int)((max_ny - 1 + kPTile - 1) / kPTile) : 1; }
 }  // namespace
 
-size_t wh::pulse_scratch_bytes(int B, int64_t max_ny) {
-  const size_t mt = (size_t)pulse_tiles(max_ny);
-  return (((size_t)B * mt * 256 + 255) & ~(size_t)255) + (((size_t)B * mt * sizeof(int32_t) + 255) & ~(size_t)255);
+wh::TimeBaseLayout::TimeBaseLayout(Carve& c, int B, int64_t ny_tot, int64_t pulse_cap, int64_t max_ny) {
+  const int64_t slots = B * pulse_cap, tiles = (int64_t)B * pulse_tiles(max_ny);
+  phase = c.take<double>(ny_tot);
+  vuv = c.take<uint8_t>(ny_tot);
+  pt = c.take<double>(slots);
+  pi = c.take<int64_t>(slots);
+  ps = c.take<double>(slots);
+  pn = c.take<int64_t>(slots);
+  pc = c.take<int32_t>(B);
+  masks = c.take<uint8_t>(tiles * 256);
+  tile_cnt = c.take<int32_t>(tiles);
 }
 
 int wh::launch_pulses(wh_ctx* ctx, hipStream_t st, int B, int64_t max_ny, const SynUtt* d_meta, const double* tp,
-                      const double* f0, const double* vuv, double fs, double f0_low_limit, const int64_t* h_y_off, char* ws,
+                      const double* f0, const double* vuv, double fs, double f0_low_limit, const int64_t* h_y_off, void* ws,
                       const TimeBaseLayout& lay) {
-  double* d_phase = reinterpret_cast<double*>(ws + lay.o_phase);
-  uint8_t* d_vuv = reinterpret_cast<uint8_t*>(ws + lay.o_vuv);
-  double* d_pt = reinterpret_cast<double*>(ws + lay.o_pt);
-  int64_t* d_pi = reinterpret_cast<int64_t*>(ws + lay.o_pi);
-  double* d_ps = reinterpret_cast<double*>(ws + lay.o_ps);
-  int64_t* d_pn = reinterpret_cast<int64_t*>(ws + lay.o_pn);
-  int32_t* d_pc = reinterpret_cast<int32_t*>(ws + lay.o_pc);
+  double *d_phase = lay.phase.at(ws), *d_pt = lay.pt.at(ws), *d_ps = lay.ps.at(ws);
+  int64_t *d_pi = lay.pi.at(ws), *d_pn = lay.pn.at(ws);
+  int32_t *d_pc = lay.pc.at(ws), *d_tc = lay.tile_cnt.at(ws);
+  uint8_t *d_vuv = lay.vuv.at(ws), *d_masks = lay.masks.at(ws);
   WH_LAUNCH(ctx, st, "prep_kernel", prep_kernel, dim3((unsigned)((max_ny + 255) / 256), B), dim3(256), 0, d_meta, tp,
             f0, vuv, fs, f0_low_limit, d_phase, d_vuv);
   if (int rc = exact_cumsum_segments(ctx, st, d_phase, h_y_off, B)) return rc;
   const int mt = pulse_tiles(max_ny);
-  uint8_t* d_masks = reinterpret_cast<uint8_t*>(ws + lay.o_px);
-  int32_t* d_tc = reinterpret_cast<int32_t*>(ws + lay.o_px + (((size_t)B * mt * 256 + 255) & ~(size_t)255));
   WH_LAUNCH(ctx, st, "pulse_mark_kernel", pulse_mark_kernel, dim3(mt, B), dim3(256), 0, d_meta, d_phase, mt, d_masks,
             d_tc);
   WH_LAUNCH(ctx, st, "pulse_scan_kernel", pulse_scan_kernel, dim3(B), dim3(256), 0, d_meta, mt, d_tc, d_pc,
@@ -729,36 +735,31 @@ extern "C" int wh_synthesis_timebase(wh_ctx* ctx, void* stream, const wh_batch* 
   int64_t max_ny = 0;
   if (int rc = wh::fill_syn_meta("wh_synthesis_timebase", b, h_y_off, h_t0, h_dt, pulse_cap, nullptr, nullptr, meta, &max_ny)) return rc;
   const int64_t ny_tot = h_y_off[B];
-  const wh::TimeBaseLayout lay(B, ny_tot, pulse_cap, max_ny);
-  size_t off = lay.end;
-  const size_t o_pb = off; off += lay.al(sizeof(int64_t) * (B + 1));
-  const size_t o_rec = off; off += lay.al(sizeof(PulseRec) * B * pulse_cap);
-  if (int rc = wh::ws_reserve(ctx, off)) return rc;
+  wh::Carve carve;
+  const wh::TimeBaseLayout lay(carve, B, ny_tot, pulse_cap, max_ny);
+  const auto r_pb = carve.take<int64_t>(B + 1);
+  const auto r_rec = carve.take<PulseRec>(B * pulse_cap);
+  if (int rc = wh::ws_reserve(ctx, carve)) return rc;
   ctx->timebase.valid = false;
-  char* ws = reinterpret_cast<char*>(ctx->ws);
+  void* ws = ctx->ws;
   SynUtt* d_meta = nullptr;
-  const uint8_t* d_vuv = reinterpret_cast<const uint8_t*>(ws + lay.o_vuv);
-  int64_t* d_pb = reinterpret_cast<int64_t*>(ws + o_pb);
-  const double* d_pt = reinterpret_cast<const double*>(ws + lay.o_pt);
-  const int64_t* d_pi = reinterpret_cast<const int64_t*>(ws + lay.o_pi);
-  const double* d_ps = reinterpret_cast<const double*>(ws + lay.o_ps);
-  const int64_t* d_pn = reinterpret_cast<const int64_t*>(ws + lay.o_pn);
-  const int32_t* d_pc = reinterpret_cast<const int32_t*>(ws + lay.o_pc);
+  int64_t* d_pb = r_pb.at(ws);
+  const int32_t* d_pc = lay.pc.at(ws);
   if (int rc = wh::persistent_upload(ctx, st, "syn.tbmeta", meta, &d_meta)) return rc;
   if (int rc = wh::launch_pulses(ctx, st, B, max_ny, d_meta, tp, f0, vuv, fs, f0_low_limit, h_y_off, ws, lay)) return rc;
   WH_LAUNCH(ctx, st, "pulse_base_kernel", pulse_base_kernel, dim3(1), dim3(64), 0, d_pc, B, d_pb);
   WH_LAUNCH(ctx, st, "pulse_frames_kernel", pulse_frames_kernel, dim3((unsigned)((pulse_cap + 255) / 256), B),
-            dim3(256), 0, d_meta, tp, d_pt, d_pi, d_ps, d_pn, d_vuv, d_pc, d_pb,
-            reinterpret_cast<PulseRec*>(ws + o_rec));
+            dim3(256), 0, d_meta, tp, lay.pt.at(ws), lay.pi.at(ws), lay.ps.at(ws), lay.pn.at(ws), lay.vuv.at(ws), d_pc,
+            d_pb, r_rec.at(ws));
   wh_ctx::TimeBase& t = ctx->timebase;
   t.valid = true;
   t.n_utt = B;
   t.pulse_cap = pulse_cap;
   t.ny_tot = ny_tot;
   t.frames = b->total_frames;
-  t.o_vuv = lay.o_vuv; t.o_pt = lay.o_pt; t.o_pi = lay.o_pi; t.o_ps = lay.o_ps; t.o_pn = lay.o_pn; t.o_pc = lay.o_pc; t.o_pb = o_pb;
-  t.o_rec = o_rec;
-  t.o_phase = lay.o_phase;
+  t.phase = lay.phase; t.vuv = lay.vuv; t.pt = lay.pt; t.pi = lay.pi; t.ps = lay.ps; t.pn = lay.pn; t.pc = lay.pc;
+  t.pb = r_pb;
+  t.rec = r_rec;
   t.f_off.assign(b->h_frame_off.begin(), b->h_frame_off.begin() + B);
   return 0;
 }
@@ -776,12 +777,12 @@ extern "C" int wh_synthesis_timebase_read(wh_ctx* ctx, void* stream, int n_utt, 
     return wh::fail_msg("wh_synthesis_timebase_read", "n_utt, pulse_cap or n_samples are not the time base's");
   WH_ENTER(ctx);
   WH_CHECK(hipStreamSynchronize((hipStream_t)stream));
-  const char* ws = reinterpret_cast<const char*>(ctx->ws);
+  const void* ws = ctx->ws;
   const int B = t.n_utt;
   std::vector<int32_t> count((size_t)B);
   std::vector<int64_t> base((size_t)B + 1);
-  WH_CHECK(hipMemcpy(count.data(), ws + t.o_pc, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
-  WH_CHECK(hipMemcpy(base.data(), ws + t.o_pb, sizeof(int64_t) * (B + 1), hipMemcpyDeviceToHost));
+  WH_CHECK(hipMemcpy(count.data(), t.pc.at(ws), sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+  WH_CHECK(hipMemcpy(base.data(), t.pb.at(ws), sizeof(int64_t) * (B + 1), hipMemcpyDeviceToHost));
   for (int u = 0; u < B; ++u) {
     if (count[u] < 0 || count[u] > pulse_cap || base[0] != 0 || base[u + 1] - base[u] != count[u])
       return wh::fail_msg("wh_synthesis_timebase_read", "the pulse counts in the workspace are not a time base's");
@@ -793,7 +794,7 @@ extern "C" int wh_synthesis_timebase_read(wh_ctx* ctx, void* stream, int n_utt, 
   if (total < 0 || total > (int64_t)B * pulse_cap)
     return wh::fail_msg("wh_synthesis_timebase_read", "the pulse counts in the workspace are not a time base's");
   std::vector<PulseRec> rec((size_t)total);
-  if (total > 0) WH_CHECK(hipMemcpy(rec.data(), ws + t.o_rec, sizeof(PulseRec) * (size_t)total, hipMemcpyDeviceToHost));
+  if (total > 0) WH_CHECK(hipMemcpy(rec.data(), t.rec.at(ws), sizeof(PulseRec) * (size_t)total, hipMemcpyDeviceToHost));
   for (int64_t g = 0; g < total; ++g) {
     const PulseRec& r = rec[(size_t)g];
     const int64_t f0 = (r.u >= 0 && r.u < B) ? t.f_off[(size_t)r.u] : 0;
@@ -809,12 +810,12 @@ extern "C" int wh_synthesis_timebase_read(wh_ctx* ctx, void* stream, int n_utt, 
   if (h_time) {  // p_time lies in pulse slots: pulse i of utterance u at u * pulse_cap + i
     for (int u = 0; u < B; ++u) {
       if (count[u] > 0)
-        WH_CHECK(hipMemcpy(h_time + base[u], ws + t.o_pt + sizeof(double) * (size_t)u * (size_t)pulse_cap,
+        WH_CHECK(hipMemcpy(h_time + base[u], t.pt.at(ws) + (size_t)u * (size_t)pulse_cap,
                            sizeof(double) * (size_t)count[u], hipMemcpyDeviceToHost));
     }
   }
-  if (h_phase && n_samples > 0) WH_CHECK(hipMemcpy(h_phase, ws + t.o_phase, sizeof(double) * (size_t)n_samples, hipMemcpyDeviceToHost));
-  if (h_vuv_s && n_samples > 0) WH_CHECK(hipMemcpy(h_vuv_s, ws + t.o_vuv, (size_t)n_samples, hipMemcpyDeviceToHost));
+  if (h_phase && n_samples > 0) WH_CHECK(hipMemcpy(h_phase, t.phase.at(ws), sizeof(double) * (size_t)n_samples, hipMemcpyDeviceToHost));
+  if (h_vuv_s && n_samples > 0) WH_CHECK(hipMemcpy(h_vuv_s, t.vuv.at(ws), (size_t)n_samples, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -843,12 +844,13 @@ extern "C" int wh_synthesis_plan(wh_ctx* ctx, void* stream, const wh_batch* b, c
   std::vector<SynUtt> meta;
   int64_t max_ny = 0;
   if (int rc = wh::fill_syn_meta("wh_synthesis_plan", b, h_y_off, h_t0, h_dt, pulse_cap, nullptr, nullptr, meta, &max_ny)) return rc;
-  const wh::TimeBaseLayout lay(B, h_y_off[B], pulse_cap, max_ny);
-  if (int rc = wh::ws_reserve(ctx, lay.end)) return rc;
-  char* ws = reinterpret_cast<char*>(ctx->ws);
+  wh::Carve carve;
+  const wh::TimeBaseLayout lay(carve, B, h_y_off[B], pulse_cap, max_ny);
+  if (int rc = wh::ws_reserve(ctx, carve)) return rc;
+  void* ws = ctx->ws;
   SynUtt* d_meta = nullptr;
-  const int64_t* d_pn = reinterpret_cast<const int64_t*>(ws + lay.o_pn);
-  const int32_t* d_pc = reinterpret_cast<const int32_t*>(ws + lay.o_pc);
+  const int64_t* d_pn = lay.pn.at(ws);
+  const int32_t* d_pc = lay.pc.at(ws);
   if (int rc = wh::persistent_upload(ctx, st, "syn.meta", meta, &d_meta)) return rc;
   ctx->timebase.valid = false;  // (this call lays the workspace out its own way)
   if (int rc = wh::launch_pulses(ctx, st, B, max_ny, d_meta, tp, f0, vuv, fs, 0.0, h_y_off, ws, lay)) return rc;

@@ -71,3 +71,31 @@ def test_harvest_other_search_ranges(floor, ceil, period):
     assert np.array_equal(d["temporal_positions"], o["temporal_positions"])
     assert np.array_equal(d["vuv"], o["vuv"])
     assert np.max(np.abs(d["f0"] - o["f0"])) < 1e-6
+
+
+def test_harvest_ragged_batch_of_short_utterances():
+    """24 utterances of 50 to 300 ms in one call: the contour back end's share of the workspace is carved exactly from the
+    per-utterance frame counts, and short utterances are where its five regions leave the least room after rounding —
+    every utterance of the batch against the oracle run on it alone."""
+    from oracle import pitch_harvest
+    from world._synthetic import synth_utterance
+    from world.batch import WorldBatch
+    from world.harvest import harvest_device
+
+    fs = 16000
+    src = synth_utterance(41, fs, 1.6)[6000:]  # (voiced from sample 3684 to 16483)
+    lengths = [800, 1200, 1600, 2400, 4800]
+    ref = {n: pitch_harvest.harvest_np(src[:n], fs) for n in lengths}
+    assert len(ref[800]["f0"]) == 11 and np.all(ref[800]["vuv"] == 1)
+    xs = [src[:lengths[u % 5]] for u in range(24)]
+    wb = WorldBatch()
+    batch, x_d, tp_d = wb.upload(xs, fs)
+    with wb.rt.on_stream():
+        f0_d, vuv_d = harvest_device(wb.rt, batch, x_d, tp_d, fs)
+    f0, vuv = f0_d.cpu().numpy(), vuv_d.cpu().numpy()
+    assert wb.rt.take_flags() == [0] * 16
+    for u, x in enumerate(xs):
+        o = ref[len(x)]
+        s = slice(int(batch.frame_off[u]), int(batch.frame_off[u + 1]))
+        assert np.array_equal(vuv[s], o["vuv"]), u
+        assert np.max(np.abs(f0[s] - o["f0"])) < 1e-6, u

@@ -44,6 +44,24 @@ def test_every_launch_goes_through_the_helper():
     assert not found, found
 
 
+def test_every_workspace_layout_goes_through_the_carver():
+    """wh::Carve / wh::Region (csrc/wh_arena.h) is the one place that rounds a scratch region to 256 bytes and turns an
+    offset into a typed pointer: no other file rounds by hand or casts `workspace + offset` by hand."""
+    import glob
+
+    csrc = os.path.join(ROOT, "python-world_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(files) > 40 and os.path.join(csrc, "wh_arena.h") in files
+    found = []
+    for path in files:
+        if os.path.basename(path) == "wh_arena.h":
+            continue
+        for n, line in enumerate(open(path).read().splitlines(), 1):
+            if "& ~(size_t)255" in line or re.search(r"reinterpret_cast<.*\((ws|d_ws) \+", line):
+                found.append((os.path.basename(path), n, line.strip()))
+    assert not found, found
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
 
