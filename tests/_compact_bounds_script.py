@@ -1,16 +1,11 @@
-"""Helper of tests/test_hip_compact_bounds.py: runs in a process whose WH_LIB is the bounds build
-(tools/build_variants.py bounds=...;wh_apbands:-DWH_BOUNDS=1: ap_from_bands_kernel and ap_gate_kernel index their global and
-LDS buffers through wh::ckp there).  Prints one JSON line."""
-import json
+"""Helper of tests/test_hip_compact_bounds.py: runs in a process whose WH_LIB is the bounds build (tests/_variants.py,
+bounds: ap_from_bands_kernel and ap_gate_kernel of wh_apbands.hip index their global and LDS buffers through wh::ckp
+there).  The inputs of tests/test_hip_compact.py's bitwise tests and of its end-to-end test."""
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "python-world_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import _variants as V
 
 
 def main():
@@ -21,23 +16,19 @@ def main():
     from world.batch import WorldBatch
     from world.d4c import aperiodicity_from_bands_device
 
-    out = {"bounds_build": _hip.bounds_build(), "cases": []}
     wb = WorldBatch(0)
     rt = wb.rt
+    rep = V.Report(rt)
 
     def case(name, xs, fs):
         enc = wb.encode(xs, fs, f0_method="dio", want_coarse=True)
         with rt.on_stream():
             back = aperiodicity_from_bands_device(rt, enc.coarse_ap, enc.ap_gate, fs, enc.fft_size)
-        eq = bool(torch.equal(back, enc.aperiodicity))
-        fl = rt.take_flags()
-        out["cases"].append({"name": name, "frames": enc.batch.total_frames, "equal": eq, "flag": fl[_hip.FLAG_OOB],
-                             "flags": fl, "record": list(_hip.bounds_last())})
+        rep.case(name, frames=enc.batch.total_frames, equal=bool(torch.equal(back, enc.aperiodicity)))
 
     # the inputs of tests/test_hip_compact.py's bitwise tests
-    gold = os.path.join(ROOT, "tests", "golden")
     for tag in ("syn16k", "syn48k"):
-        g = np.load(os.path.join(gold, "golden_%s.npz" % tag))
+        g = np.load(os.path.join(V.HERE, "golden", "golden_%s.npz" % tag))
         case(tag, [g["x"]], int(g["fs"]))
     fs = 16000
     rng = np.random.RandomState(12)
@@ -56,11 +47,9 @@ def main():
     W = wmain.World()
     for req in (False, True):
         dats = W.decode_compact_batch(W.encode_compact_batch(fs, xs, n0=40, is_requiem=req), seed=7)
-        fl = _hip.Runtime.get().take_flags()
-        out["cases"].append({"name": "facade requiem=%s" % req, "frames": sum(len(d["f0"]) for d in dats),
-                             "equal": bool(all(np.isfinite(d["out"]).all() for d in dats)), "flag": fl[_hip.FLAG_OOB],
-                             "flags": fl, "record": list(_hip.bounds_last())})
-    print("BOUNDS_JSON " + json.dumps(out))
+        rep.case("facade requiem=%s" % req, rt=_hip.Runtime.get(), frames=sum(len(d["f0"]) for d in dats),
+                 equal=bool(all(np.isfinite(d["out"]).all() for d in dats)))
+    rep.emit()
 
 
 if __name__ == "__main__":

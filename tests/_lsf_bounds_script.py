@@ -1,16 +1,7 @@
-"""Helper of tests/test_hip_lsf_bounds.py: runs in a process whose WH_LIB is the bounds build
-(tools/build_variants.py lsf_bounds=wh_api:-DWH_BOUNDS=1;wh_lsf:-DWH_BOUNDS=1: the three kernels of csrc/wh_lsf.hip index
-their global buffers, their tables and their LDS through wh::ckp there).  The case list of tests/test_hip_lsf.py
-(tests/_lsf_cases.py), the refinement predictors and the degenerate rows.  Prints one JSON line."""
-import json
-import os
-import sys
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-for p in (ROOT, os.path.join(ROOT, "python-world_amd"), HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+"""Helper of tests/test_hip_lsf_bounds.py: runs in a process whose WH_LIB is the bounds build (tests/_variants.py,
+lsf_bounds: the three kernels of csrc/wh_lsf.hip index their global buffers, their tables and their LDS through wh::ckp
+there).  The case list of tests/test_hip_lsf.py (tests/_lsf_cases.py), the refinement predictors and the degenerate rows."""
+import _variants as V
 
 
 def main():
@@ -18,14 +9,13 @@ def main():
     from world import _hip
 
     rt = _hip.Runtime.get()
-    out = {"bounds_build": _hip.bounds_build(), "cases": []}
+    rep = V.Report(rt)
 
     def record(name, bad, expect_lsf_flag):
-        fl = rt.take_flags()
-        lsf_flag = int(fl[_hip.FLAG_LSF] != 0)
-        fl[_hip.FLAG_LSF] = 0
-        out["cases"].append({"name": name, "equal": not bad, "flags": fl, "lsf_flag_as_expected": lsf_flag == expect_lsf_flag,
-                             "record": list(_hip.bounds_last()), "first": bad[:3]})
+        # WH_FLAG_LSF is these inputs' expected answer, not a finding: reported on its own and cleared from the flags
+        c = rep.case(name, equal=not bad, first=bad[:3])
+        c["lsf_flag_as_expected"] = int(c["flags"][_hip.FLAG_LSF] != 0) == expect_lsf_flag
+        c["flags"][_hip.FLAG_LSF] = 0
 
     for case in lc.kernel_cases():
         record(case.name, lc.compare(lc.run(rt, case), lc.reference(case)), 0)
@@ -38,7 +28,7 @@ def main():
     got.update({k: v for k, v in lc.run_lsf(rt, want["a"]).items() if k != "guards"})
     got.update({k: v for k, v in lc.run_envelope(rt, want["ex"], 129).items() if k != "guards"})
     record("degenerate rows", lc.compare(got, want), 1)
-    print("BOUNDS_JSON " + json.dumps(out))
+    rep.emit()
 
 
 if __name__ == "__main__":

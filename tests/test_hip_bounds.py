@@ -14,40 +14,13 @@ size, a Harvest + Requiem batch and a 48 kHz utterance run clean; the transform 
 each of a handful of shapes, stays inside its LDS buffers and the twiddle block; the selection probe and the two spectral
 probes (csrc/wh_d4c_probe.hip, csrc/wh_spectral_probe.hip), one call per shape on the inputs that reach furthest — every selection
 round and refinement level, the replica with every bin a node — stay inside theirs."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
+
+import _variants as V
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-BOUNDS_TUS = ("wh_api", "wh_cheaptrick", "wh_stonemask", "wh_harvest", "wh_hv_front", "wh_hv_refine", "wh_hv_contour", "wh_timebase", "wh_synthesis", "wh_peak", "wh_requiem", "wh_d4c",
-              "wh_apbands", "wh_d4c_probe", "wh_fft_probe", "wh_spectral_probe")
-VARIANT = os.path.join(ROOT, "python-world_amd", "lib", "variants", "libworld_hip_bounds.so")
-
-
-def _build_variant():
-    spec = "bounds=" + ";".join("%s:-DWH_BOUNDS=1" % tu for tu in BOUNDS_TUS)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "build_variants.py"), spec], capture_output=True,
-                       text=True, timeout=1500)
-    assert r.returncode == 0 and "bounds ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-
-
-@pytest.fixture(scope="module")
-def report():
-    lib = os.path.join(ROOT, "python-world_amd", "lib", "libworld_hip.so")
-    if not os.path.exists(VARIANT) or os.path.getmtime(VARIANT) < os.path.getmtime(lib):
-        _build_variant()
-    env = dict(os.environ, WH_LIB=VARIANT)
-    r = subprocess.run([sys.executable, os.path.join(HERE, "_bounds_script.py")], capture_output=True, text=True, env=env,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("BOUNDS_JSON ")][-1]
-    return json.loads(line[len("BOUNDS_JSON "):])
+report = V.report_fixture("bounds", "_bounds_script.py", timeout=900)
 
 
 def test_the_checker_fires_on_the_positive_control(report):

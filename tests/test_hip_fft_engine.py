@@ -299,21 +299,10 @@ def test_d_wave_local_transform_has_the_bits_of_the_workgroup_wide_one(s):
 
 @pytest.fixture(scope="module")
 def nocontract_report():
-    import json
-    import subprocess
-    import sys
+    import _variants as V
 
-    import _fft_variant_script as V
-
-    from world import _hip
-
-    if not os.path.exists(V.VARIANT) or os.path.getmtime(V.VARIANT) < os.path.getmtime(_hip.LIB_PATH):
-        V.build_variant()
-    r = subprocess.run([sys.executable, V.__file__], capture_output=True, text=True, env=dict(os.environ, WH_LIB=V.VARIANT),
-                       timeout=300)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("FFT_VARIANT_JSON ")][-1]
-    return json.loads(line[len("FFT_VARIANT_JSON "):])
+    V.ensure("nocontract")
+    return V.run_script("_fft_variant_script.py", "nocontract", timeout=300)
 
 
 @pytest.mark.parametrize("nt", [128, 64])

@@ -2,39 +2,14 @@
 a checked pointer under -DWH_BOUNDS=1).  A variant of its own (wh_api and wh_manifold instrumented) runs the random
 stacks of tests/test_hip_manifold.py at the tile edges, a tap with segments and kept columns, the TIMIT networks on the
 stored MCEP and a ragged batch with window 2: zero out-of-range records, and the same results still."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
+
+import _variants as V
+from world._hip import FLAG_OOB
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-BOUNDS_TUS = ("wh_api", "wh_manifold")
-VARIANT = os.path.join(ROOT, "python-world_amd", "lib", "variants", "libworld_hip_manifold_bounds.so")
-
-
-def build_variant():
-    spec = "manifold_bounds=" + ";".join("%s:-DWH_BOUNDS=1" % tu for tu in BOUNDS_TUS)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "build_variants.py"), spec], capture_output=True,
-                       text=True, timeout=1500)
-    assert r.returncode == 0 and "manifold_bounds ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-
-
-@pytest.fixture(scope="module")
-def report():
-    lib = os.path.join(ROOT, "python-world_amd", "lib", "libworld_hip.so")
-    if not os.path.exists(VARIANT) or os.path.getmtime(VARIANT) < os.path.getmtime(lib):
-        build_variant()
-    env = dict(os.environ, WH_LIB=VARIANT)
-    r = subprocess.run([sys.executable, os.path.join(HERE, "_manifold_bounds_script.py")], capture_output=True, text=True,
-                       env=env, timeout=600)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("BOUNDS_JSON ")][-1]
-    return json.loads(line[len("BOUNDS_JSON "):])
+report = V.report_fixture("manifold_bounds", "_manifold_bounds_script.py")
 
 
 def test_variant_is_a_bounds_build(report):
@@ -42,5 +17,5 @@ def test_variant_is_a_bounds_build(report):
 
 
 def test_every_case_stays_inside_its_buffers(report):
-    bad = [c for c in report["cases"] if c["flag"] or c["record"] != [0, 0, 0, 0] or not c["ok"]]
+    bad = [c for c in report["cases"] if c["flags"][FLAG_OOB] or c["record"] != [0, 0, 0, 0] or not c["ok"]]
     assert len(report["cases"]) == 43 and bad == []

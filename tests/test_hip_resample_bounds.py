@@ -2,39 +2,14 @@
 checked pointer under -DWH_BOUNDS=1).  A variant of its own (wh_api and wh_resample instrumented) runs the short
 lengths at every kernel path — filter rows in registers, through L1, input spans beyond LDS, the 1280-factor and 4096
 bounds — and a mixed batch of 12 utterances at 6 rates: zero out-of-range records, and scipy's results still."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
+
+import _variants as V
+from world._hip import FLAG_OOB
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-BOUNDS_TUS = ("wh_api", "wh_resample")
-VARIANT = os.path.join(ROOT, "python-world_amd", "lib", "variants", "libworld_hip_resample_bounds.so")
-
-
-def build_variant():
-    spec = "resample_bounds=" + ";".join("%s:-DWH_BOUNDS=1" % tu for tu in BOUNDS_TUS)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "build_variants.py"), spec], capture_output=True,
-                       text=True, timeout=1500)
-    assert r.returncode == 0 and "resample_bounds ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-
-
-@pytest.fixture(scope="module")
-def report():
-    lib = os.path.join(ROOT, "python-world_amd", "lib", "libworld_hip.so")
-    if not os.path.exists(VARIANT) or os.path.getmtime(VARIANT) < os.path.getmtime(lib):
-        build_variant()
-    env = dict(os.environ, WH_LIB=VARIANT)
-    r = subprocess.run([sys.executable, os.path.join(HERE, "_resample_bounds_script.py")], capture_output=True, text=True,
-                       env=env, timeout=600)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("BOUNDS_JSON ")][-1]
-    return json.loads(line[len("BOUNDS_JSON "):])
+report = V.report_fixture("resample_bounds", "_resample_bounds_script.py")
 
 
 def test_variant_is_a_bounds_build(report):
@@ -42,10 +17,10 @@ def test_variant_is_a_bounds_build(report):
 
 
 def test_short_lengths_at_every_path_stay_inside_their_buffers(report):
-    bad = [c for c in report["cases"] if c["flag"] or c["record"] != [0, 0, 0, 0] or not c["equal"]]
+    bad = [c for c in report["cases"] if c["flags"][FLAG_OOB] or c["record"] != [0, 0, 0, 0] or not c["equal"]]
     assert len(report["cases"]) == 88 and bad == []
 
 
 def test_mixed_batch_stays_inside_its_buffers(report):
     m = report["mixed"]
-    assert m["flag"] == 0 and m["record"] == [0, 0, 0, 0] and m["equal"], m
+    assert m["flags"][FLAG_OOB] == 0 and m["record"] == [0, 0, 0, 0] and m["equal"], m

@@ -3,46 +3,13 @@ two kernels is a checked pointer under -DWH_BOUNDS=1 — the waveform, the row m
 dimensions, the bin table, the twiddles, the chain's two LDS buffers, the staged roots, the run's sums, the overlap-add
 rows and the output).  A variant of its own (wh_api and wh_specfilter instrumented) runs the case list of
 tests/test_hip_specfilter.py: zero out-of-range records, and the shipped library's bits."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
+
+import _variants as V
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-BOUNDS_TUS = ("wh_api", "wh_specfilter")
-VARIANT = os.path.join(ROOT, "python-world_amd", "lib", "variants", "libworld_hip_specfilter_bounds.so")
-
-
-def build_variant():
-    spec = "specfilter_bounds=" + ";".join("%s:-DWH_BOUNDS=1" % tu for tu in BOUNDS_TUS)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "build_variants.py"), spec], capture_output=True,
-                       text=True, timeout=1500)
-    assert r.returncode == 0 and "specfilter_bounds ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-
-
-def _run(lib):
-    env = dict(os.environ)
-    env.pop("WH_LIB", None)
-    if lib:
-        env["WH_LIB"] = lib
-    r = subprocess.run([sys.executable, os.path.join(HERE, "_specfilter_bounds_script.py")], capture_output=True, text=True,
-                       env=env, timeout=600)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("BOUNDS_JSON ")][-1]
-    return json.loads(line[len("BOUNDS_JSON "):])
-
-
-@pytest.fixture(scope="module")
-def reports():
-    lib = os.path.join(ROOT, "python-world_amd", "lib", "libworld_hip.so")
-    if not os.path.exists(VARIANT) or os.path.getmtime(VARIANT) < os.path.getmtime(lib):
-        build_variant()
-    return _run(VARIANT), _run(None)
+reports = V.report_fixture("specfilter_bounds", "_specfilter_bounds_script.py", shipped=True)
 
 
 def test_variant_is_a_bounds_build(reports):
