@@ -92,6 +92,11 @@ int wh_math_table_read(double* h_out, int64_t n_entries);
  * transforms of n = 512 points, interleaved (re, im) doubles, in -> out; inverse = 1: exp(+2 pi i k j / n), not divided by
  * n.  (gt, snt): threads per transform group and per workgroup, one of (64, 64), (128, 256), (256, 256). */
 int wh_fft_probe(wh_ctx* ctx, void* stream, int n, int gt, int snt, int inverse, const double* in, double* out, int64_t count);
+/* Test hook: the packed workgroup reductions of csrc/wh_reduce.h (block_sum2 | block_sum3 | block_sum5: k = 2 | 3 | 5) in one
+ * workgroup of nt threads (64, 128, 256 or 512) on DEVICE data (csrc/wh_reduce_probe.hip).  in: k rows of nt doubles, value
+ * k of thread t at in[k nt + t].  out: 2 k doubles per thread, out[t 2 k + j]: j < k the packed routine's total of value j as
+ * thread t received it, j >= k the same total by one wave_sum per value and the waves added in ascending order from 0.0. */
+int wh_reduce_probe(wh_ctx* ctx, void* stream, int nt, int k, const double* in, double* out);
 /* Test hook: the workgroup-wide transforms of csrc/wh_fft.h on DEVICE data, at the shapes the kernels instantiate them
  * with (csrc/wh_fft_probe.hip lists them; any other shape fails with a message).  kind 0: fft_lds<n, inverse, nt, snt, maxr>,
  * n complex -> n complex; 1: fft_lds_from_regs<n, false, nt, maxr>, the same, the input read straight into the registers of

@@ -47,6 +47,7 @@ TU_FLAGS = {
     "wh_d4c.hip": ["-ffp-contract=fast-honor-pragmas"],
     "wh_apbands.hip": ["-ffp-contract=fast-honor-pragmas"],
     "wh_d4c_probe.hip": ["-ffp-contract=fast-honor-pragmas"],  # (a test hook: the D4C headers as wh_d4c.hip compiles them)
+    "wh_reduce_probe.hip": ["-ffp-contract=fast-honor-pragmas"],  # (a test hook: wh_reduce.h as wh_d4c.hip compiles it)
     "wh_cheaptrick.hip": ["-ffp-contract=fast-honor-pragmas"],
     "wh_fft_probe.hip": ["-ffp-contract=fast-honor-pragmas"],  # (a test hook: the transforms as most of their callers compile them)
     "wh_spectral_probe.hip": ["-ffp-contract=fast-honor-pragmas"],  # (a test hook: wh_spectral.h as wh_cheaptrick.hip compiles it)

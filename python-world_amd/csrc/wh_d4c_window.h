@@ -208,15 +208,27 @@ __device__ __forceinline__ void d4c_window_regs(wh::ckp<const double> WH_RESTRIC
     rel = rel > rhi ? rhi : rel;
     return xb[rel];
   };
-  const int nq = L >= N ? Q : (L + FT - 1) / FT;  // rows that hold window samples (workgroup-uniform)
-  // All Q loads are issued unconditionally (the index is clamped: always a valid address; rows past the window read its
-  // last sample, one line for the whole wave) and the rows past nq zeroed by a select.  Written as `if (q < nq) out[q] =
-  // sample(..)` the compiler made a chain of conditional blocks, each WAITING for its load before the next block's and
-  // copying the whole array between them: nq dependent global round trips and ~25 register moves per row.
+  // rows that hold window samples: workgroup-uniform, and said so (a scalar: the row tests below are scalar branches)
+  const int nq = __builtin_amdgcn_readfirstlane(L >= N ? Q : (L + FT - 1) / FT);
+  // All loads of a round are issued unconditionally (the index is clamped: always a valid address; rows past the window
+  // read its last sample, one line for the whole wave) and the rows past nq zeroed by a select.  Written as `if (q < nq)
+  // out[q] = sample(..)` the compiler made a chain of conditional blocks, each WAITING for its load before the next block's
+  // and copying the whole array between them: nq dependent global round trips and ~25 register moves per row.
+  // Two rounds to choose from, each straight-line: a window of at most Q / 2 rows (every pitch above 62.5 Hz at N = 2048)
+  // loads Q / 2 rows and its upper rows are plain zeros — no clamp, address, load or select for them.
+  if (nq <= Q / 2) {
 #pragma unroll
-  for (int q = 0; q < Q; ++q) out[q] = sample(threadIdx.x + q * FT);
+    for (int q = 0; q < Q / 2; ++q) out[q] = sample(threadIdx.x + q * FT);
 #pragma unroll
-  for (int q = 0; q < Q; ++q) out[q] = q < nq ? out[q] : 0.0;
+    for (int q = 0; q < Q / 2; ++q) out[q] = q < nq ? out[q] : 0.0;
+#pragma unroll
+    for (int q = Q / 2; q < Q; ++q) out[q] = 0.0;
+  } else {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) out[q] = sample(threadIdx.x + q * FT);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) out[q] = q < nq ? out[q] : 0.0;
+  }
   const double rot_s = ws.rot_s, rot_c = ws.rot_c;
   const double c0 = ws.base_c * e_tid.y - ws.base_s * e_tid.x;  // phase of this thread's first sample: base * E[tid]
   const double s0 = ws.base_s * e_tid.y + ws.base_c * e_tid.x;

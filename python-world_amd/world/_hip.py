@@ -51,6 +51,7 @@ SIGNATURES = {
     "wh_math_probe": (_int, [_vp, _vp, _int, _vp, _vp, ctypes.c_int64]),
     "wh_math_table_read": (_int, [_vp, ctypes.c_int64]),
     "wh_fft_probe": (_int, [_vp, _vp, _int, _int, _int, _int, _vp, _vp, ctypes.c_int64]),
+    "wh_reduce_probe": (_int, [_vp, _vp, _int, _int, _vp, _vp]),
     "wh_fft_engine_probe": (_int, [_vp, _vp, _int, _int, _int, _int, _int, _int, _vp, _vp, ctypes.c_int64]),
     "wh_twiddle_read": (_int, [_vp, _vp, ctypes.c_int64]),
     "wh_d4c_select_probe": (_int, [_vp, _vp, _int, _int, _int, _vp, _vp, ctypes.c_int64]),
