@@ -689,6 +689,56 @@ int wh_spectral_filter(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_
 int wh_wsola(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_off, const int64_t* h_y_off, const int64_t* h_pos_off,
              const int64_t* h_pos, int hop, int tol, const double* h_win, const double* x, double* y, int32_t* delta);
 
+/* ---- Exemplar-based conversion: k-nearest-neighbour search and frame selection by Viterbi (no counterpart) ------------ */
+/* ABI 124; tests/_exemplar_reference.py is the same contract in NumPy.  The target speaker's aligned
+ * frames are kept as a database; every source frame takes the K entries whose source side is nearest (wh_knn), and a
+ * Viterbi pass picks one per frame, trading closeness against the continuity of the chosen target frames
+ * (wh_frame_select): every converted envelope is a frame the target speaker produced, nothing is averaged.
+ *
+ * wh_knn: q [n_q] rows of d columns with row stride ldq, db [n_db] rows with row stride lddb (DEVICE FP64; the strides
+ * in elements, >= d: column slices are fine); 1 <= d <= 160, 1 <= K <= 32, n_db <= 2^31 - 1.
+ *   distance  s(n, r) = sum over c = 0 .. d-1 ascending, from +0.0, of (q[n][c] - db[r][c]) * (q[n][c] - db[r][c]): every
+ *             difference, product and sum rounded on its own (wh_dtw's local cost without the square root).
+ *   key       s, or +inf where s is NaN.
+ *   result    the candidates of query n are all rows r, less those with excl_lo[n] <= r < excl_hi[n] when the two DEVICE
+ *             int32 arrays [n_q] are given (both or neither).  idx[n][0 .. K) (DEVICE int32, row stride K) are the K
+ *             candidates that are smallest under the total order (key ascending, then r ascending), in that order;
+ *             dist[n][k] (DEVICE FP64) is the key.  Slots beyond the number of candidates hold idx = -1, dist = +inf.
+ *   splits    0: the library's choice; n >= 1 (at most 65535): the database is cut into n consecutive ranges of
+ *             ceil(n_db / n) rows, every range keeps a list of its own and a second kernel merges the lists under the same
+ *             order.  Because the order is total, neither the cut nor the tiling shows in the result: every value of
+ *             splits gives the same bytes.
+ * Part of the contract: no atomics; a query's result does not depend on the other queries of the call; no address and no
+ * trip count depends on a feature value (the lists are updated by K compare-selects).  n_q == 0 or n_db == 0 is no error
+ * (n_db == 0: every slot is empty).  Wrong arguments — a limit exceeded, a stride below d, a null pointer where one is
+ * needed, one exclusion array without the other, splits < 0 — fail before anything is launched, with the reason in
+ * wh_last_error. */
+int wh_knn(wh_ctx* ctx, void* stream, const double* q, int64_t n_q, int64_t ldq, const double* db, int64_t n_db, int64_t lddb,
+           int d, int K, const int32_t* excl_lo, const int32_t* excl_hi, int splits, int32_t* idx, double* dist);
+
+/* wh_frame_select: per utterance of b (its frame offsets; F frames) one slot of every frame's K candidates.  idx, tc
+ * [total_frames][K] are wh_knn's two outputs (DEVICE); y [n_db] rows of dy columns with row stride ldy >= dy (DEVICE FP64,
+ * 1 <= dy <= 64); succ [n_db] (DEVICE int32) is the database row that follows each row in the target recording; weight is
+ * finite and >= 0.
+ *   validity  a slot with idx < 0 or idx >= n_db is invalid: its rows are never read and its accumulated cost is +inf.  As
+ *             a predecessor, slot j of frame t-1 is also invalid where succ[idx(t-1, j)] lies outside [0, n_db).  The
+ *             caller guarantees that slot 0 of every frame is valid.
+ *   chain     A(0, k) = tc(0, k).  For t >= 1 and valid k: cc(j, k) = sum over c ascending, from +0.0, of the squared
+ *             difference of y[idx(t, k)][c] and y[succ[idx(t-1, j)]][c], unfused;  v(j) = A(t-1, j) + weight * cc(j, k), one
+ *             product and one sum, each rounded, and +inf for an invalid j;  best = v(0), and for j = 1 .. K-1 ascending
+ *             v(j) replaces it only where strictly smaller (a NaN never replaces);  A(t, k) = tc(t, k) + best, the chosen j
+ *             is the back-pointer (one byte per frame and slot in the context's scratch).
+ *   end       the smallest k whose A(F-1, k) is strictly smallest (the same scan over k).
+ *   outputs   sel[f] (DEVICE int32 [total_frames]) = idx of the chosen slot; slot[f] the slot, may be NULL;
+ *             total[u] (DEVICE FP64 [n_utt]) = A(F-1, k*), 0.0 for an empty utterance; acc_out, may be NULL: A as
+ *             [total_frames][K], a test hook like wh_dtw's.
+ * Non-finite rows give unspecified values and a well-formed selection (ties and NaNs fall to slot 0).  An utterance's
+ * result does not depend on the batch it is in; no atomics; the results repeat bit for bit.  One workgroup per utterance:
+ * the frames are one sequential chain.  Wrong arguments fail before anything is launched. */
+int wh_frame_select(wh_ctx* ctx, void* stream, const wh_batch* b, const int32_t* idx, const double* tc, int K, const double* y,
+                    int64_t n_db, int64_t ldy, int dy, const int32_t* succ, double weight, int32_t* sel, int32_t* slot,
+                    double* total, double* acc_out);
+
 /* ---- 16-bit PCM at the batch boundary (the reference's WAV usage: example/prosody.py:12-13,57) ---------------------- */
 /* x[i] = pcm[i] / (2^15 - 1); pcm[i] = int16(trunc(y[i] * 2^15)) (low 16 bits, like NumPy's astype on the reference's
  * platform).  DEVICE pointers: the 2-byte samples cross PCIe instead of the 8-byte ones. */

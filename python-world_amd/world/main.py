@@ -544,6 +544,30 @@ class World(object):
             raise NotImplementedError("convert_voice(devices=...): run one WorldBatch per device instead")
         return convert_voice_dict(dat, model, mode, **kw)
 
+    # ---- exemplar-based conversion: frame selection from the target's own frames (world/exemplar.py) -------------------
+    @_hip.serialised
+    def build_exemplars(self, dats_a, dats_b, n0=40, lsf_order=None, radius=None, devices=None, **kw):
+        """A frame database from parallel utterances: encode() dicts of a source speaker and of a target speaker, pair u
+        the same sentence.  The pairs are aligned as fit_conversion aligns them; row r of the database is target frame r
+        (static + delta rows of the mel-cepstral coefficients 1 .. n0-1, or of the ``lsf_order`` angles) next to the
+        source's rows at the aligned frame.  Returns a world.exemplar.FrameDatabase (``kw``: windows, normalise, ...)."""
+        from .exemplar import build_exemplars_dicts
+        if devices is not None:
+            raise NotImplementedError("build_exemplars(devices=...): run one WorldBatch per device instead")
+        return build_exemplars_dicts(dats_a, dats_b, n0, lsf_order, radius, **kw)
+
+    @_hip.serialised
+    def convert_voice_exemplar(self, dat, db, k=16, weight=1.0, mode="frames", devices=None, **kw):
+        """An encode() dict of the source speaker -> a new dict whose spectrogram is made of frames the target speaker
+        produced: for every frame the ``k`` database rows nearest on the source side, one of them chosen by a Viterbi
+        pass whose concatenation cost is ``weight`` times the distance to what followed the previous choice in the
+        target's recording.  ``mode`` 'frames': the chosen rows themselves; 'mlpg': a trajectory through their static
+        and delta rows.  Coefficient 0, f0, vuv and aperiodicity are carried over; decode() takes it."""
+        from .exemplar import convert_voice_exemplar_dict
+        if devices is not None:
+            raise NotImplementedError("convert_voice_exemplar(devices=...): run one WorldBatch per device instead")
+        return convert_voice_exemplar_dict(dat, db, k, weight, mode, **kw)
+
     # ---- a per-frame spectral gain on a recording: vocoder-free conversion (world/specfilter.py) -----------------------
     @_hip.serialised
     def filter_waveform(self, fs, x, dat_num, dat_den=None, devices=None):
