@@ -689,6 +689,58 @@ int wh_spectral_filter(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_
 int wh_wsola(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_off, const int64_t* h_y_off, const int64_t* h_pos_off,
              const int64_t* h_pos, int hop, int tol, const double* h_win, const double* x, double* y, int32_t* delta);
 
+/* ---- Pitch-synchronous overlap-add: a new f0 contour and timing for a recording (no counterpart) --------------------- */
+/* ABI 125; tests/_psola_reference.py is the same contract in NumPy.  Grains two periods wide are cut
+ * around pitch marks of the recording and re-spaced at the target period: the grain spacing sets f0, the grain content —
+ * and with it the spectral envelope — stays.  Unlike wh_wsola + wh_resample_poly the target may be a contour, and the
+ * formants do not move with f0.
+ * Per call: grid G, 1 .. 4096, the spacing in samples of the three tracks; unvoiced_hop U, 1 .. 2048, the mark spacing
+ * in unvoiced stretches; tol, 0 .. 512; pmin, 2 .. 2048, the smallest voiced period; smin, 1 .. 2048, the smallest
+ * synthesis step; norm, 0 or 1.  PMAX = 2048.  eff(p) = p when pmin <= p <= PMAX, else 0 (unvoiced).  At most 65535
+ * utterances per call (stage C's launch has one grid row per utterance).
+ * Per utterance u: x[0 .. n), n = h_x_off[u+1] - h_x_off[u]; y[0 .. n_out), n_out = h_y_off[u+1] - h_y_off[u]; each at
+ * most 2^40 samples, each mark list at most 2^31 - 1 entries; a read of x outside [0, n) is 0.0.  Three DEVICE tracks:
+ * per_a (int32, Ka = n / G + 1 entries at h_pa_off[u]: the analysis period at input sample k G), per_s (int32,
+ * Ks = n_out / G + 1 entries at h_ps_off[u]: the target period at output sample k G) and src (int64, Ks entries at
+ * h_ps_off[u]: the input sample that output sample k G corresponds to, clamped to +- 2^62 before use).  The offsets'
+ * differences must be Ka and Ks.  The tracks are data no host check sees: no value in them takes an access out of range
+ * or a loop beyond its capacity.
+ *   stage A   analysis marks, a sequential chain.  n == 0: none.  a_0 = 0.  At mark i: P_i = eff(per_a[min(Ka - 1, a_i / G)]).
+ *             a_i >= n: the last mark, Ma = i + 1 (the mark at or beyond the end belongs to the list).  P_i == 0:
+ *             a_{i+1} = a_i + U.  Otherwise h = P_i / 2, D_i = min(tol, P_i / 4), the template is t[j] = x[a_i - h + j],
+ *             j < P_i, candidate d in [-D_i, D_i] is g_d[j] = x[a_i + P_i + d - h + j], and score and choice are wh_wsola's:
+ *             num = sum t[j] g_d[j], den = sum g_d[j] g_d[j], from +0.0, j ascending, unfused; num / sqrt(den) when den > 0
+ *             else 0.0; NaN counts as -inf; the greatest score, then the smallest |d|, then the negative one.
+ *             a_{i+1} = a_i + P_i + d*.  Every step is at least m = min(U, pmin - min(tol, pmin / 4)), so
+ *             Ma <= ceil(n / m) + 1: h_mark_off[u+1] - h_mark_off[u] must be at least that.
+ *   stage B   synthesis marks, a sequential integer chain.  None when n_out == 0 or Ma == 0 (y is then +0.0).  s_0 = 0.
+ *             At mark j: k = min(Ks - 1, s_j / G); c = src[k] + (s_j - k G); sel_j = the i that minimises |a_i - c|, the
+ *             lower i on a tie (src need not be monotone); flip_j = 1 exactly when j >= 1, P_sel_j == 0,
+ *             sel_j == sel_{j-1} and flip_{j-1} == 0 (a repeated unvoiced grain is read backwards).  s_j >= n_out: the
+ *             last mark, Ms = j + 1.  Otherwise with Q = eff(per_s[k]): if Q > 0 and P_sel > 0, sp = a_{sel+1} - a_sel
+ *             (P_sel at the last mark) and step = max(smin, (sp Q + P_sel / 2) / P_sel) in integers; else step = U.
+ *             s_{j+1} = s_j + step.  h_smark_off[u+1] - h_smark_off[u] must be at least ceil(n_out / min(U, smin)) + 1.
+ *   stage C   overlap-add, a gather.  Grain j has i = sel_j, fb = P_i if P_i > 0 else U, Lw = a_i - a_{i-1} (fb when
+ *             i == 0), Rw = a_{i+1} - a_i (fb when i is the last mark).  With tau = t - s_j the grain contributes to y[t]
+ *             iff -Lw < tau < Rw: u = |tau| / (tau < 0 ? Lw : Rw), one IEEE divide of two exact doubles;
+ *             w = 1 - (u u) (3 - 2 u), every operation rounded on its own (within 0.01 of a Hanning half; complementary
+ *             halves sum to 1; no transcendental); v = x[a_i + (flip_j ? -tau : tau)]; num += w v and W += w, j ascending,
+ *             from +0.0, unfused.  y[t] = num / max(W, 1.0) when norm, else num; no grain gives +0.0.
+ * Outputs besides y, all DEVICE and each may be NULL (the context's scratch then holds it): marks (int64) and mark_period
+ * (int32, P_i) at h_mark_off[u]; n_marks (int32 [n_utt]); smarks (int64), sel (int32) and flip (uint8) at h_smark_off[u];
+ * n_smarks (int32 [n_utt]).  Entries beyond the counts are not written.
+ * Part of the contract: no atomics — the same bits from run to run, and for an utterance alone as inside any batch; every
+ * access is range-tested; a NaN or Inf in x reaches only the outputs of the grains that read it and, through the scores,
+ * the later marks of the same utterance — no other utterance.  h_*: HOST; y must not overlap x.  Stages A and B are one
+ * sequential chain per utterance (one workgroup, one wave): a small batch of long utterances leaves most of the device
+ * idle; stage C is chip-wide.  n_utt == 0 is no error; wrong arguments (the limits, offsets that decrease, a track of
+ * another length, a capacity too small) fail before anything is launched, with the reason in wh_last_error. */
+int wh_psola(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_off, const int64_t* h_y_off, const int64_t* h_pa_off,
+             const int64_t* h_ps_off, const int64_t* h_mark_off, const int64_t* h_smark_off, int grid, int unvoiced_hop,
+             int tol, int pmin, int smin, int norm, const double* x, const int32_t* per_a, const int32_t* per_s,
+             const int64_t* src, double* y, int64_t* marks, int32_t* mark_period, int32_t* n_marks, int64_t* smarks,
+             int32_t* sel, uint8_t* flip, int32_t* n_smarks);
+
 /* ---- Exemplar-based conversion: k-nearest-neighbour search and frame selection by Viterbi (no counterpart) ------------ */
 /* ABI 124; tests/_exemplar_reference.py is the same contract in NumPy.  The target speaker's aligned
  * frames are kept as a database; every source frame takes the K entries whose source side is nearest (wh_knn), and a

@@ -39,6 +39,8 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 #     min_phase_response's own pragma.
 #   * wh_wsola.hip (waveform-similarity overlap-add) has no entry below and no pragma: its scores are sums of products
 #     rounded one by one, compared bit for bit with tests/_wsola_reference.py.
+#   * wh_psola.hip (pitch-synchronous overlap-add) likewise: the scores and the window's cubic are rounded operation by
+#     operation, compared bit for bit with tests/_psola_reference.py.
 #   * wh_peak.hip and wh_philox_probe.hip were parts of wh_synthesis.hip, which has no entry below (it contracts by
 #     pragma): they need none either.
 # The F0 stages (DIO, StoneMask, Harvest — wh_harvest.hip, wh_hv_front.hip, wh_hv_refine.hip, wh_hv_contour.hip —, SWIPE') and the synthesis TIME BASE (wh_timebase.hip: no pragma anywhere in it)

@@ -120,6 +120,8 @@ SIGNATURES = {
     "wh_spectral_filter": (_int, [_vp, _vp, _int, _c_i64p, _c_i64p, _c_i64p, ctypes.POINTER(ctypes.c_int32), _c_i64p, _int,
                                   _vp, ctypes.c_int64, _vp, ctypes.c_int64, _int, ctypes.POINTER(_dbl), _int, _vp, _vp]),
     "wh_wsola": (_int, [_vp, _vp, _int, _c_i64p, _c_i64p, _c_i64p, _c_i64p, _int, _int, ctypes.POINTER(_dbl), _vp, _vp, _vp]),
+    "wh_psola": (_int, [_vp, _vp, _int, _c_i64p, _c_i64p, _c_i64p, _c_i64p, _c_i64p, _c_i64p, _int, _int, _int, _int, _int, _int,
+                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "wh_knn": (_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64, _int, _int, _vp, _vp,
                       _int, _vp, _vp]),
     "wh_frame_select": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, ctypes.c_int64, ctypes.c_int64, _int, _vp, _dbl, _vp, _vp,

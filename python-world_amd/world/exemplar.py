@@ -383,7 +383,8 @@ def convert_compact(ce, db, k=16, weight=1.0, mode="frames", exclude=None, min_g
 def convert_waveform(wb, batch, x_d, ce, db, hop=None, **kw):
     """Vocoder-free conversion by frame selection: convert_compact(ce, db, **kw), then the recording ``x_d`` of ``batch``
     filtered by the converted over the source envelope (world.specfilter.differential_device), as gmm.convert_waveform.
-    Returns (y_d in x's layout, the converted CompactEncoding, info)."""
+    Returns (y_d in x's layout, the converted CompactEncoding, info).  The f0 stays the recording's: to move it first,
+    world.psola.modify_device(.., pitch=world.tsm.log_f0_ratio(a, b)) leaves the formants in place."""
     from .specfilter import differential_device
 
     converted, info = convert_compact(ce, db, **kw)

@@ -476,7 +476,9 @@ def convert_waveform(wb, batch, x_d, ce, model, windows=CONVERSION_WINDOWS, mode
     """Vocoder-free conversion: convert_compact(ce, model), then the recording ``x_d`` of ``batch`` (WorldBatch.upload's
     pair, the waveforms ``ce`` was encoded from) filtered by the converted over the source envelope, both as coded — the
     coding error cancels in the ratio, excitation, phase and aperiodicity stay the recording's
-    (world.specfilter.differential_device).  Returns (y_d in x's layout, the converted CompactEncoding)."""
+    (world.specfilter.differential_device).  Returns (y_d in x's layout, the converted CompactEncoding).  The f0 stays the
+    recording's: to move it to the target speaker's first, world.psola.modify_device(.., pitch=world.tsm.log_f0_ratio(a, b))
+    leaves the formants in place (world.tsm.shift_pitch_device moves them with f0)."""
     from .specfilter import differential_device
 
     converted = convert_compact(ce, model, windows, mode, min_gap)

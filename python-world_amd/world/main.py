@@ -608,6 +608,26 @@ class World(object):
             raise NotImplementedError("shift_pitch_waveform(devices=...): run one WorldBatch per device instead")
         return shift_pitch_waveform_numpy(fs, x, ratio, hop, tol)
 
+    # ---- a new f0 contour and timing for a recording: pitch-synchronous overlap-add (world/psola.py) --------------------
+    @_hip.serialised
+    def modify_waveform(self, fs, x, dat, pitch=1.0, f0=None, duration=1.0, devices=None):
+        """The recording ``x`` with f0 x ``pitch`` (or the per-frame target ``f0`` on dat['temporal_positions']) and
+        ``duration`` x as long, by pitch-synchronous overlap-add around the periods of ``dat`` = encode(fs, x): grains are
+        re-spaced, not resampled, so the formants stay in place (shift_pitch_waveform moves them with f0)."""
+        from .psola import modify_waveform_numpy
+        if devices is not None:
+            raise NotImplementedError("modify_waveform(devices=...): run one WorldBatch per device instead")
+        return modify_waveform_numpy(fs, x, dat, pitch, f0, duration)
+
+    @_hip.serialised
+    def set_pitch_waveform(self, fs, x, dat, time, value, devices=None):
+        """set_pitch_contour for a recording: the contour (time [s], value [Hz], 0 = unvoiced) is interpolated onto
+        dat['temporal_positions'] with the voiced rule and imposed on ``x`` at its own duration."""
+        from .psola import set_pitch_waveform_numpy
+        if devices is not None:
+            raise NotImplementedError("set_pitch_waveform(devices=...): run one WorldBatch per device instead")
+        return set_pitch_waveform_numpy(fs, x, dat, time, value)
+
     # ---- modification (all in place on the dict, like the reference) ------------------------------------------
     def scale_pitch(self, dat, factor):
         """world/main.py:154-162."""

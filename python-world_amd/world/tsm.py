@@ -191,7 +191,8 @@ def shift_pitch_device(rt, x_d, x_off, fs, ratio, hop=None, tol=None, window=('k
     q / p (world.resample.resample_device: scipy.signal.resample_poly(.., q, p) bit for bit), then trimmed or zero-padded to
     the input's length.  Returns (y_d in x's layout — utterance u at x_off[u]:x_off[u+1] —, the Fraction used).  The
     resampling moves the whole spectrum: the formants move by p / q with f0; the differential filter trained on the
-    shifted recording moves the envelope to the target."""
+    shifted recording moves the envelope to the target.  The alternative that leaves the formants in place — and takes a
+    contour as well as a ratio — is world.psola.modify_device(.., pitch=log_f0_ratio(a, b))."""
     from .resample import resample_device
 
     where = "shift_pitch_device"
