@@ -129,6 +129,21 @@ int wh_d4c_runs_probe(wh_ctx* ctx, void* stream, int n, int which, double fs, co
  * BandWindow) at cheaptrick_kernel's (n, ft): (256 | 512 | 1024, 128), (2048 | 4096, 256).  Arguments as above. */
 int wh_spectral_probe(wh_ctx* ctx, void* stream, int n, int ft, int which, double fs, const double* f0,
                       const double* reach_or_half, const double* in, double* out, int64_t count);
+/* Test hook: Harvest's back end — hv_prune_kernel and the contour kernels (FixF0Contour, SmoothF0, the pick onto the frame
+ * grid) — on candidate maps the CALLER supplies (csrc/wh_hv_probe.hip), through the launchers wh_harvest calls.  n_utt
+ * utterances of h_nf1[u] >= 1 frames of 1 ms, concatenated; output frames h_frame_off[u] .. h_frame_off[u + 1] (at least one
+ * each) at the times tp (seconds, DEVICE).  rf0 / rsc (DEVICE, pool_n doubles each): candidate frequencies and scores;
+ * h_lst (HOST, one per 1 ms frame): (first pool slot << 8) | count, count <= 105 — a frame's candidates in the reference's
+ * row order, an absent row being a zero.  keep (DEVICE, 4 uint32 per 1 ms frame): bit k = entry k of the frame's list
+ * survives; mode 0 reads it, mode 1 runs the prune and writes it.  mode 2 runs the smoothing and the pick alone: `rows`
+ * holds the step-4 contour in row 4 on entry, and rf0 / rsc / h_lst / keep are not used.  Out: f0_out / vuv_out (DEVICE, per
+ * output frame); rows (DEVICE): per utterance six rows of nf1 doubles at 6 x (frames in front of it) — base, steps 1 to 4,
+ * smoothed; h_nsec (HOST, [n_utt]) and h_secs (HOST, [n_utt][sec_cap][5]): step 3's sections as (first, last, extended
+ * first, extended last, kept); more than sec_cap sections fail.  Waits for `stream`. */
+int wh_harvest_contour_probe(wh_ctx* ctx, void* stream, int mode, int n_utt, const int64_t* h_nf1, const int64_t* h_frame_off,
+                             const double* tp, const double* rf0, const double* rsc, int64_t pool_n, const int64_t* h_lst,
+                             uint32_t* keep, double* f0_out, double* vuv_out, double* rows, int32_t* h_nsec, int32_t* h_secs,
+                             int64_t sec_cap);
 /* The same flags without a host wait, for callers that keep a pipeline of batches in flight:
  *   wh_flags_post — enqueue (one 16-lane kernel on `stream`) the publication of the flags raised by everything before
  *     it on the stream to a pinned host word per flag, and clear them on the device (discard != 0: clear them

@@ -44,7 +44,8 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 #   * wh_peak.hip and wh_philox_probe.hip were parts of wh_synthesis.hip, which has no entry below (it contracts by
 #     pragma): they need none either.
 # The F0 stages (DIO, StoneMask, Harvest — wh_harvest.hip, wh_hv_front.hip, wh_hv_refine.hip, wh_hv_contour.hip —, SWIPE') and the synthesis TIME BASE (wh_timebase.hip: no pragma anywhere in it)
-# stay unfused: voicing decisions and pulse positions are bit-exact against the reference.
+# stay unfused: voicing decisions and pulse positions are bit-exact against the reference.  wh_hv_probe.hip (a test hook:
+# Harvest's back end on caller-supplied candidate maps) has no entry below either: it is built like wh_hv_contour.hip.
 TU_FLAGS = {
     "wh_d4c.hip": ["-ffp-contract=fast-honor-pragmas"],
     "wh_apbands.hip": ["-ffp-contract=fast-honor-pragmas"],

@@ -662,4 +662,49 @@ int hv_launch_contour(wh_ctx* ctx, hipStream_t st, const HvPlan& p, const HvDev&
   return 0;
 }
 
+// Test hook (wh_hv_probe.hip): hc_smooth_kernel and hc_pick_kernel alone, with the grids hv_launch_contour gives them, on
+// six rows per utterance that the caller supplies (only row 4, the step-4 contour, is read).  FixF0Contour cannot leave
+// a voiced run shorter than 7 frames, so the layouts that fill the smoothing scratch are reachable only this way.
+int hv_launch_smooth_pick(wh_ctx* ctx, hipStream_t st, const HvPlan& p, const HvDev& d, const double* rows_in,
+                          const double* tp, double* f0_out, double* vuv_out) {
+  const HcLayout l(p);
+  HcUtt* d_hc = nullptr;
+  double *d_rows = l.rows.at(d.ct), *d_ch = l.ch.at(d.ct);
+  int32_t* d_runs = l.runs.at(d.ct);
+  if (int rc = persistent_upload(ctx, st, "hv.contour", l.hc, &d_hc)) return rc;
+  WH_CHECK(hipMemcpyAsync(d_rows, rows_in, sizeof(double) * p.f1_tot * 6, hipMemcpyDeviceToDevice, st));
+  WH_CHECK(hipMemsetAsync(l.ns.at(d.ct), 0, sizeof(int32_t) * p.B, st));  // (no section table in this form)
+  WH_LAUNCH(ctx, st, "hc_smooth_kernel", hc_smooth_kernel, dim3(p.B), dim3(256), 0, d.meta, d_hc, d_rows, d_runs, d_ch);
+  WH_LAUNCH(ctx, st, "hc_pick_kernel", hc_pick_kernel, dim3((unsigned)((p.max_nf + 255) / 256), p.B), dim3(256), 0,
+            d.meta, d_hc, d_rows, tp, f0_out, vuv_out);
+  return 0;
+}
+
+// Test hook (wh_hv_probe.hip): what the last hv_launch_contour (or hv_launch_smooth_pick) of this plan left in the share.
+// rows_out (DEVICE): per utterance six rows of nf1 doubles at 6 f1_off — base, s1, s2, s3, s4, smoothed.  h_nsec (HOST,
+// [B]): sections of step 3; h_secs (HOST, [B][sec_cap][5]): each section's (st, ed, r0, r1, kept).  Waits for `st`.
+int hv_read_contour(hipStream_t st, const HvPlan& p, const HvDev& d, double* rows_out, int32_t* h_nsec, int32_t* h_secs,
+                    int64_t sec_cap) {
+  const HcLayout l(p);
+  WH_CHECK(hipMemcpyAsync(rows_out, l.rows.at(d.ct), sizeof(double) * p.f1_tot * 6, hipMemcpyDeviceToDevice, st));
+  std::vector<HcSec> secs(l.secs.count);
+  WH_CHECK(hipMemcpyAsync(h_nsec, l.ns.at(d.ct), sizeof(int32_t) * p.B, hipMemcpyDeviceToHost, st));
+  WH_CHECK(hipMemcpyAsync(secs.data(), l.secs.at(d.ct), sizeof(HcSec) * secs.size(), hipMemcpyDeviceToHost, st));
+  WH_CHECK(hipStreamSynchronize(st));
+  for (int u = 0; u < p.B; ++u) {
+    if (h_nsec[u] < 0 || h_nsec[u] > l.hc[u].rcap) return fail_msg("hv_read_contour", "section count out of range");
+    if (h_nsec[u] > sec_cap) return fail_msg("hv_read_contour", "more sections than sec_cap");
+    for (int k = 0; k < h_nsec[u]; ++k) {
+      const HcSec& s = secs[l.hc[u].sec_base + k];
+      int32_t* o = h_secs + ((int64_t)u * sec_cap + k) * 5;
+      o[0] = s.st;
+      o[1] = s.ed;
+      o[2] = s.r0;
+      o[3] = s.r1;
+      o[4] = s.kept;
+    }
+  }
+  return 0;
+}
+
 }  // namespace wh

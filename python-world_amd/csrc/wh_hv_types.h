@@ -95,5 +95,11 @@ int hv_launch_prune(wh_ctx* ctx, hipStream_t st, const HvPlan& p, const HvDev& d
 Region<char> hv_carve_contour(Carve& c, const HvPlan& p);
 int hv_launch_contour(wh_ctx* ctx, hipStream_t st, const HvPlan& p, const HvDev& d, const double* tp, double* f0_out,
                       double* vuv_out, double* dbg_f0_1ms);
+// test hooks (wh_hv_probe.hip): the smoothing and the pick alone on caller-supplied rows; the rows and the section table
+// the back end left in its share (rows_out: DEVICE; h_nsec [B], h_secs [B][sec_cap][5] = (st, ed, r0, r1, kept): HOST)
+int hv_launch_smooth_pick(wh_ctx* ctx, hipStream_t st, const HvPlan& p, const HvDev& d, const double* rows_in,
+                          const double* tp, double* f0_out, double* vuv_out);
+int hv_read_contour(hipStream_t st, const HvPlan& p, const HvDev& d, double* rows_out, int32_t* h_nsec, int32_t* h_secs,
+                    int64_t sec_cap);
 
 }  // namespace wh

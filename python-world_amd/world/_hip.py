@@ -57,6 +57,8 @@ SIGNATURES = {
     "wh_d4c_select_probe": (_int, [_vp, _vp, _int, _int, _int, _vp, _vp, ctypes.c_int64]),
     "wh_d4c_runs_probe": (_int, [_vp, _vp, _int, _int, _dbl, _vp, _vp, _vp, _vp, ctypes.c_int64]),
     "wh_spectral_probe": (_int, [_vp, _vp, _int, _int, _int, _dbl, _vp, _vp, _vp, _vp, ctypes.c_int64]),
+    "wh_harvest_contour_probe": (_int, [_vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, ctypes.c_int64]),
     "wh_flags_post": (_int, [_vp, _vp, _int]),
     "wh_flags_poll": (_int, [_vp, ctypes.POINTER(ctypes.c_int32)]),
     "wh_dio": (_int, [_vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _int, _vp, _vp, _vp, _vp, _vp, _int,
