@@ -140,6 +140,13 @@ inline int allow_lds(K kernel, size_t bytes) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   return e == hipSuccess ? 0 : fail("hipFuncSetAttribute", e);
 }
+// Utterance u of a host offset table (n_utt + 1 entries): where it starts and how long it is; false when either is negative
+// (the entry points answer "offsets must start at or above 0 and be monotone").
+inline bool utt_span(const int64_t* h_off, int u, int64_t* start, int64_t* len) {
+  *start = h_off[u];
+  *len = h_off[u + 1] - h_off[u];
+  return *start >= 0 && *len >= 0;
+}
 // f(std::integral_constant<int, N>()) for the transform length fft_size = N of a kernel family that is instantiated at the
 // powers of two from 512 to MAXN (4096: the synthesis kernels; 8192: D4C and its gate); false: not one of them.
 template <int MAXN = 4096, class F>

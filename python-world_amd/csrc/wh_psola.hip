@@ -9,7 +9,8 @@
 //                         mark the template (P doubles) and the candidate region (P + 2 D doubles) are staged in LDS,
 //                         zero-filled outside the utterance; thread i runs the two add chains of the candidates i,
 //                         i + 256, .. side by side, j ascending, each product and sum rounded on its own (build.py's
-//                         default -ffp-contract=off); one workgroup argmax on wh_wsola's key (score, -|d|, d < 0).
+//                         default -ffp-contract=off); one workgroup argmax on the key (score, -|d|, d < 0):
+//                         wh::sim_search (wh_simsearch.h), the search that wh_wsola.hip calls too.
 //   psola_smarks_kernel   stage B, one wave per utterance: the synthesis marks are one sequential integer chain.  Per
 //                         mark a 64-way search of the increasing list of analysis marks (three rounds for 10 s of
 //                         speech), the flip rule and the step; the grain's centre and its two half widths go to scratch.
@@ -20,17 +21,14 @@
 // verified, and every read of x is range-tested.  No atomics.
 // ================================================================================================
 #include "wh_host.h"
-#include "wh_device.h"
+#include "wh_simsearch.h"
 
 #include <algorithm>
-#include <limits>
 
 namespace {
 
-constexpr int kPsMaxPeriod = 2048, kPsMaxTol = 512, kPsMaxGrid = 4096, kPsMaxHop = 2048;
-constexpr int kPsThreads = 256;
-constexpr int kPsWaves = kPsThreads / WH_WAVE;
-constexpr int kPsMaxPerThread = (2 * kPsMaxTol + 1 + kPsThreads - 1) / kPsThreads;  // 5
+constexpr int kPsMaxPeriod = 2048, kPsMaxTol = wh::kSimMaxTol, kPsMaxGrid = 4096, kPsMaxHop = 2048;
+constexpr int kPsThreads = wh::kSimThreads;  // (the search's workgroup: wh_simsearch.h)
 constexpr int kPsTile = 256;
 
 struct PsUtt {
@@ -53,21 +51,14 @@ __device__ __forceinline__ double ps_read(const wh::ckp<const double>& xu, int64
 
 __device__ __forceinline__ int ps_eff(int p, int pmin) { return (p >= pmin && p <= kPsMaxPeriod) ? p : 0; }
 
-// a is the better candidate: the greater score, then the smaller |shift|, then the negative shift (scores are never NaN here)
-__device__ __forceinline__ bool ps_better(double sa, int da, double sb, int db) {
-  if (sa != sb) return sa > sb;
-  const int aa = da < 0 ? -da : da, ab = db < 0 ? -db : db;
-  return aa != ab ? aa < ab : da < db;
-}
-
 template <int U>
 __global__ __launch_bounds__(kPsThreads) void psola_marks_kernel(const PsUtt* __restrict__ meta, PsParams pr, int dmax,
                                                                  const double* __restrict__ x_, const int32_t* __restrict__ per_a_,
                                                                  int64_t* __restrict__ marks_, int32_t* __restrict__ period_,
                                                                  int32_t* __restrict__ n_marks_) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ double s_score_[kPsWaves];
-  __shared__ int s_delta_[kPsWaves];
+  __shared__ double s_score_[wh::kSimWaves];
+  __shared__ int s_delta_[wh::kSimWaves];
   const PsUtt m = meta[blockIdx.x];
   const int tid = threadIdx.x;
   const wh::ckp<int32_t> n_marks = wh::ck_make(n_marks_, gridDim.x, wh::WH_CK_OUT);
@@ -78,8 +69,8 @@ __global__ __launch_bounds__(kPsThreads) void psola_marks_kernel(const PsUtt* __
   // (wh::ckp<T> is T* in every shipped build; the bounds build checks each access against the range named here)
   const wh::ckp<double> tpl = wh::ck_make(reinterpret_cast<double*>(smem), kPsMaxPeriod, wh::WH_CK_LDS_MAIN);
   const wh::ckp<double> reg = wh::ck_make(reinterpret_cast<double*>(smem) + kPsMaxPeriod, kPsMaxPeriod + 2 * dmax, wh::WH_CK_LDS_AUX);
-  const wh::ckp<double> s_score = wh::ck_make(s_score_, kPsWaves, wh::WH_CK_LDS_SCRATCH);
-  const wh::ckp<int> s_delta = wh::ck_make(s_delta_, kPsWaves, wh::WH_CK_LDS_SCRATCH);
+  const wh::ckp<double> s_score = wh::ck_make(s_score_, wh::kSimWaves, wh::WH_CK_LDS_SCRATCH);
+  const wh::ckp<int> s_delta = wh::ck_make(s_delta_, wh::kSimWaves, wh::WH_CK_LDS_SCRATCH);
   const wh::ckp<const double> xu = wh::ck_make(x_ + m.x_off, m.n, wh::WH_CK_WAVEFORM);
   const wh::ckp<const int32_t> per_a = wh::ck_make(per_a_ + m.pa_off, m.ka, wh::WH_CK_IN);
   const wh::ckp<int64_t> marks = wh::ck_make(marks_ + m.mark_off, m.mark_cap, wh::WH_CK_OUT);
@@ -100,59 +91,13 @@ __global__ __launch_bounds__(kPsThreads) void psola_marks_kernel(const PsUtt* __
       a += pr.hop;
       continue;
     }
-    const int h = P / 2, D = min(pr.tol, P / 4), R = P + 2 * D, ncand = 2 * D + 1;
+    const int h = P / 2, D = min(pr.tol, P / 4), R = P + 2 * D;
     const int64_t tb = a - h, rb = a + P - D - h;
     // (the mark before's readers are behind its second barrier)
     for (int j = tid; j < P; j += kPsThreads) tpl[j] = ps_read(xu, tb + j, m.n);
     for (int j = tid; j < R; j += kPsThreads) reg[j] = ps_read(xu, rb + j, m.n);
     __syncthreads();
-    // this thread's candidates: k = tid + 256 u; one beyond the list runs the last one again and is discarded
-    int k[U];
-    double num[U], den[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      k[u] = min(tid + kPsThreads * u, ncand - 1);
-      num[u] = den[u] = 0.0;
-    }
-#pragma unroll 4
-    for (int j = 0; j < (tid < ncand ? P : 0); ++j) {  // (a wave without a candidate leaves its SIMD to the others)
-      const double t = tpl[j];  // (one address for the wave: a broadcast)
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const double g = reg[k[u] + j];  // (consecutive lanes, consecutive addresses)
-        num[u] = num[u] + t * g;
-        den[u] = den[u] + g * g;
-      }
-    }
-    double best_s = -std::numeric_limits<double>::infinity();
-    int best_d = std::numeric_limits<int>::max();  // (no candidate: loses to every candidate)
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (tid + kPsThreads * u < ncand) {
-        double s = den[u] > 0 ? num[u] / sqrt(den[u]) : 0.0;
-        if (s != s) s = -std::numeric_limits<double>::infinity();
-        const int d = k[u] - D;
-        if (ps_better(s, d, best_s, best_d)) best_s = s, best_d = d;
-      }
-    }
-#pragma unroll
-    for (int off = WH_WAVE / 2; off > 0; off >>= 1) {
-      const double os = __shfl_xor(best_s, off, WH_WAVE);
-      const int od = __shfl_xor(best_d, off, WH_WAVE);
-      if (ps_better(os, od, best_s, best_d)) best_s = os, best_d = od;
-    }
-    if ((tid & (WH_WAVE - 1)) == 0) {
-      s_score[tid / WH_WAVE] = best_s;
-      s_delta[tid / WH_WAVE] = best_d;
-    }
-    __syncthreads();
-    best_s = s_score[0], best_d = s_delta[0];
-#pragma unroll
-    for (int w = 1; w < kPsWaves; ++w) {
-      const double os = s_score[w];
-      const int od = s_delta[w];
-      if (ps_better(os, od, best_s, best_d)) best_s = os, best_d = od;
-    }
+    const int best_d = wh::sim_search<U>(tpl, reg, P, D, s_score, s_delta, tid);
     // (candidate 0 always exists, so |best_d| <= D <= P / 4; the slots are rewritten behind the next mark's first barrier)
     a += P + best_d;
   }
@@ -299,14 +244,6 @@ __global__ __launch_bounds__(kPsTile) void psola_ola_kernel(const PsUtt* __restr
   if (t < m.n_out) y[t] = norm ? num / (wsum > 1.0 ? wsum : 1.0) : num;
 }
 
-template <int U>
-int launch_marks(wh_ctx* ctx, hipStream_t st, int B, size_t lds, const PsUtt* d_meta, PsParams pr, int dmax, const double* x,
-                 const int32_t* per_a, int64_t* marks, int32_t* period, int32_t* n_marks) {
-  if (int rc = wh::allow_lds(psola_marks_kernel<U>, lds)) return rc;
-  return wh::launch(ctx, st, "psola_marks_kernel", psola_marks_kernel<U>, dim3((unsigned)B), dim3(kPsThreads), lds, d_meta, pr,
-                    dmax, x, per_a, marks, period, n_marks);
-}
-
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 }  // namespace
@@ -336,14 +273,9 @@ extern "C" int wh_psola(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x
   int64_t max_out = 0;
   for (int u = 0; u < B; ++u) {
     PsUtt& m = meta[u];
-    m.x_off = h_x_off[u], m.n = h_x_off[u + 1] - h_x_off[u];
-    m.y_off = h_y_off[u], m.n_out = h_y_off[u + 1] - h_y_off[u];
-    m.pa_off = h_pa_off[u], m.ka = h_pa_off[u + 1] - h_pa_off[u];
-    m.ps_off = h_ps_off[u], m.ks = h_ps_off[u + 1] - h_ps_off[u];
-    m.mark_off = h_mark_off[u], m.mark_cap = h_mark_off[u + 1] - h_mark_off[u];
-    m.smark_off = h_smark_off[u], m.smark_cap = h_smark_off[u + 1] - h_smark_off[u];
-    if (m.x_off < 0 || m.n < 0 || m.y_off < 0 || m.n_out < 0 || m.pa_off < 0 || m.ka < 0 || m.ps_off < 0 || m.ks < 0 ||
-        m.mark_off < 0 || m.mark_cap < 0 || m.smark_off < 0 || m.smark_cap < 0)
+    if (!wh::utt_span(h_x_off, u, &m.x_off, &m.n) || !wh::utt_span(h_y_off, u, &m.y_off, &m.n_out) ||
+        !wh::utt_span(h_pa_off, u, &m.pa_off, &m.ka) || !wh::utt_span(h_ps_off, u, &m.ps_off, &m.ks) ||
+        !wh::utt_span(h_mark_off, u, &m.mark_off, &m.mark_cap) || !wh::utt_span(h_smark_off, u, &m.smark_off, &m.smark_cap))
       return wh::fail_msg(where, "offsets must start at or above 0 and be monotone");
     if (m.n > ((int64_t)1 << 40) || m.n_out > ((int64_t)1 << 40)) return wh::fail_msg(where, "an utterance is too long for one call");
     if (m.ka != m.n / grid + 1) return wh::fail_msg(where, "an utterance's analysis track must have n / grid + 1 entries");
@@ -388,16 +320,13 @@ extern "C" int wh_psola(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x
   // the template and the candidate region at the largest period (32 KB at D = 0, 40 KB at D = 512)
   const int dmax = std::min(tol, kPsMaxPeriod / 4);
   const size_t lds = sizeof(double) * (size_t)(2 * kPsMaxPeriod + 2 * dmax);
-  const int per_thread = (2 * dmax + 1 + kPsThreads - 1) / kPsThreads;  // candidates a thread runs side by side
-  static_assert(kPsMaxPerThread == 5, "one instantiation per count");
-  int rc = 0;
-  switch (per_thread) {
-    case 1: rc = launch_marks<1>(ctx, st, B, lds, d_meta, pr, dmax, x, per_a, marks, mark_period, n_marks); break;
-    case 2: rc = launch_marks<2>(ctx, st, B, lds, d_meta, pr, dmax, x, per_a, marks, mark_period, n_marks); break;
-    case 3: rc = launch_marks<3>(ctx, st, B, lds, d_meta, pr, dmax, x, per_a, marks, mark_period, n_marks); break;
-    case 4: rc = launch_marks<4>(ctx, st, B, lds, d_meta, pr, dmax, x, per_a, marks, mark_period, n_marks); break;
-    default: rc = launch_marks<5>(ctx, st, B, lds, d_meta, pr, dmax, x, per_a, marks, mark_period, n_marks); break;
-  }
+  // one instantiation per count of candidates that a thread runs side by side
+  const int rc = wh::dispatch_sim_width(dmax, [&](auto u) {
+    const auto kernel = psola_marks_kernel<decltype(u)::value>;
+    if (int e = wh::allow_lds(kernel, lds)) return e;
+    return wh::launch(ctx, st, "psola_marks_kernel", kernel, dim3((unsigned)B), dim3(kPsThreads), lds, d_meta, pr, dmax, x, per_a,
+                      marks, mark_period, n_marks);
+  });
   if (rc) return rc;
   WH_LAUNCH(ctx, st, "psola_smarks_kernel", psola_smarks_kernel, dim3((unsigned)B), dim3(WH_WAVE), 0, d_meta, pr, per_s, src,
             marks, mark_period, n_marks, smarks, sel, flip, n_smarks, d_centre, d_lw, d_rw, d_reach);

@@ -266,14 +266,10 @@ extern "C" int wh_spectral_filter(wh_ctx* ctx, void* stream, int n_utt, const in
   int64_t max_ny = 0;
   for (int u = 0; u < B; ++u) {
     SfUtt& m = meta[u];
-    m.x_off = h_x_off[u];
-    m.ny = h_x_off[u + 1] - h_x_off[u];
-    m.f_off = h_frame_off[u];
-    m.map_off = h_map_off[u];
-    m.n_win = h_map_off[u + 1] - h_map_off[u];
     m.hop = h_hop[u];
-    const int64_t nf = h_frame_off[u + 1] - h_frame_off[u];
-    if (m.x_off < 0 || m.ny < 0 || m.f_off < 0 || nf < 0 || m.map_off < 0 || m.n_win < 0)
+    int64_t nf = 0;
+    if (!wh::utt_span(h_x_off, u, &m.x_off, &m.ny) || !wh::utt_span(h_frame_off, u, &m.f_off, &nf) ||
+        !wh::utt_span(h_map_off, u, &m.map_off, &m.n_win))
       return wh::fail_msg(where, "offsets must start at or above 0 and be monotone");
     if (m.hop < 1) return wh::fail_msg(where, "hop below one sample");
     if (2 * m.hop - 1 > (int64_t)fft_size) return wh::fail_msg(where, "the window of 2 hop - 1 samples is longer than fft_size");

@@ -11,23 +11,21 @@
 //                         candidate region (L + 2 D doubles) are staged in LDS, zero-filled outside the utterance;
 //                         thread i runs the two add chains of the candidates i, i + 256, .. side by side, j ascending,
 //                         each product and sum rounded on its own (build.py's default -ffp-contract=off); one
-//                         workgroup argmax on the key (score, -|d|, d < 0), a total order.
+//                         workgroup argmax on the key (score, -|d|, d < 0), a total order.  From the staged buffers
+//                         to the winning shift this is wh::sim_search (wh_simsearch.h), shared with wh_psola.hip.
 //   wsola_ola_kernel      every output sample from the list of frame starts: at most two terms, the earlier frame first.
 // The only value-dependent index is the shift, confined to [-D, D] by construction; positions are added in unsigned
 // arithmetic (any int64 is a legal position) and every read of x is range-tested.  No atomics.
 // ================================================================================================
 #include "wh_host.h"
-#include "wh_device.h"
+#include "wh_simsearch.h"
 
 #include <algorithm>
-#include <limits>
 
 namespace {
 
-constexpr int kWsMaxHop = 1024, kWsMaxTol = 512;
-constexpr int kWsThreads = 256;
-constexpr int kWsWaves = kWsThreads / WH_WAVE;
-constexpr int kWsMaxPerThread = (2 * kWsMaxTol + 1 + kWsThreads - 1) / kWsThreads;  // 5
+constexpr int kWsMaxHop = 1024, kWsMaxTol = wh::kSimMaxTol;
+constexpr int kWsThreads = wh::kSimThreads;  // (the search's workgroup: wh_simsearch.h)
 
 struct WsUtt {
   int64_t x_off;    // first input sample
@@ -41,38 +39,29 @@ struct WsUtt {
 // x[i] for a position in unsigned arithmetic: anything outside [0, n) — negative positions wrap beyond 2^63 — reads 0.0
 __device__ __forceinline__ double ws_read(const wh::ckp<const double>& xu, uint64_t i, uint64_t n) { return i < n ? xu[(long long)i] : 0.0; }
 
-// a is the better candidate: the greater score, then the smaller |shift|, then the negative shift (scores are never NaN here)
-__device__ __forceinline__ bool ws_better(double sa, int da, double sb, int db) {
-  if (sa != sb) return sa > sb;
-  const int aa = da < 0 ? -da : da, ab = db < 0 ? -db : db;
-  return aa != ab ? aa < ab : da < db;
-}
-
 template <int U>
 __global__ __launch_bounds__(kWsThreads) void wsola_search_kernel(const WsUtt* __restrict__ meta, const int64_t* __restrict__ pos_,
                                                                   int hop, int tol, const double* __restrict__ x_,
                                                                   int64_t* __restrict__ c_, int32_t* __restrict__ delta_) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ double s_score_[kWsWaves];
-  __shared__ int s_delta_[kWsWaves];
+  __shared__ double s_score_[wh::kSimWaves];
+  __shared__ int s_delta_[wh::kSimWaves];
   const WsUtt m = meta[blockIdx.x];
   if (m.n_frames == 0) return;  // (uniform over the workgroup)
-  const int L = 2 * hop - 1, R = L + 2 * tol, ncand = 2 * tol + 1;
+  const int L = 2 * hop - 1, R = L + 2 * tol;
   const int tid = threadIdx.x;
   // (wh::ckp<T> is T* in every shipped build; the bounds build checks each access against the range named here)
   const wh::ckp<double> tpl = wh::ck_make(reinterpret_cast<double*>(smem), L, wh::WH_CK_LDS_MAIN);       // the template
-  const wh::ckp<double> reg = wh::ck_make(reinterpret_cast<double*>(smem) + L, R, wh::WH_CK_LDS_AUX);   // x[pos - D ..]
-  const wh::ckp<double> s_score = wh::ck_make(s_score_, kWsWaves, wh::WH_CK_LDS_SCRATCH);
-  const wh::ckp<int> s_delta = wh::ck_make(s_delta_, kWsWaves, wh::WH_CK_LDS_SCRATCH);
+  // (the region starts one double behind the template's odd length, on an even offset: with both LDS bases a multiple of 16
+  // bytes apart the chain loop of wh::sim_search addresses them from one pointer without a negative displacement)
+  const wh::ckp<double> reg = wh::ck_make(reinterpret_cast<double*>(smem) + L + 1, R, wh::WH_CK_LDS_AUX);  // x[pos - D ..]
+  const wh::ckp<double> s_score = wh::ck_make(s_score_, wh::kSimWaves, wh::WH_CK_LDS_SCRATCH);
+  const wh::ckp<int> s_delta = wh::ck_make(s_delta_, wh::kSimWaves, wh::WH_CK_LDS_SCRATCH);
   const wh::ckp<const double> xu = wh::ck_make(x_ + m.x_off, m.n, wh::WH_CK_WAVEFORM);
   const wh::ckp<const int64_t> pos = wh::ck_make(pos_ + m.pos_off, m.n_frames, wh::WH_CK_IN);
   const wh::ckp<int64_t> c = wh::ck_make(c_ + m.pos_off, m.n_frames, wh::WH_CK_OUT);
   const wh::ckp<int32_t> dl = wh::ck_make(delta_ ? delta_ + m.pos_off : delta_, delta_ ? m.n_frames : 0, wh::WH_CK_OUT);
   const uint64_t n = (uint64_t)m.n;
-  // this thread's candidates: k = tid + 256 u; one beyond the list runs the last one again and is discarded
-  int k[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) k[u] = min(tid + kWsThreads * u, ncand - 1);
   uint64_t c_prev = (uint64_t)pos[0];  // delta_0 = 0
   if (tid == 0) {
     c[0] = (int64_t)c_prev;
@@ -86,48 +75,7 @@ __global__ __launch_bounds__(kWsThreads) void wsola_search_kernel(const WsUtt* _
     for (int j = tid; j < L; j += kWsThreads) tpl[j] = ws_read(xu, tb + (uint64_t)j, n);
     for (int i = tid; i < R; i += kWsThreads) reg[i] = ws_read(xu, rb + (uint64_t)i, n);
     __syncthreads();
-    double num[U], den[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) num[u] = den[u] = 0.0;
-#pragma unroll 4
-    for (int j = 0; j < (tid < ncand ? L : 0); ++j) {  // (a wave without a candidate leaves its SIMD to the others)
-      const double t = tpl[j];  // (one address for the wave: a broadcast)
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const double g = reg[k[u] + j];  // (consecutive lanes, consecutive addresses)
-        num[u] = num[u] + t * g;
-        den[u] = den[u] + g * g;
-      }
-    }
-    double best_s = -std::numeric_limits<double>::infinity();
-    int best_d = std::numeric_limits<int>::max();  // (no candidate: loses to every candidate)
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (tid + kWsThreads * u < ncand) {
-        double s = den[u] > 0 ? num[u] / sqrt(den[u]) : 0.0;
-        if (s != s) s = -std::numeric_limits<double>::infinity();
-        const int d = k[u] - tol;
-        if (ws_better(s, d, best_s, best_d)) best_s = s, best_d = d;
-      }
-    }
-#pragma unroll
-    for (int off = WH_WAVE / 2; off > 0; off >>= 1) {
-      const double os = __shfl_xor(best_s, off, WH_WAVE);
-      const int od = __shfl_xor(best_d, off, WH_WAVE);
-      if (ws_better(os, od, best_s, best_d)) best_s = os, best_d = od;
-    }
-    if ((tid & (WH_WAVE - 1)) == 0) {
-      s_score[tid / WH_WAVE] = best_s;
-      s_delta[tid / WH_WAVE] = best_d;
-    }
-    __syncthreads();
-    best_s = s_score[0], best_d = s_delta[0];
-#pragma unroll
-    for (int w = 1; w < kWsWaves; ++w) {
-      const double os = s_score[w];
-      const int od = s_delta[w];
-      if (ws_better(os, od, best_s, best_d)) best_s = os, best_d = od;
-    }
+    const int best_d = wh::sim_search<U>(tpl, reg, L, tol, s_score, s_delta, tid);
     // (candidate 0 always exists, so |best_d| <= D; the slots are rewritten behind the next frame's first barrier)
     c_prev = p + (uint64_t)(int64_t)best_d;
     if (tid == 0) {
@@ -158,14 +106,6 @@ __global__ __launch_bounds__(256) void wsola_ola_kernel(const WsUtt* __restrict_
   y[t] = acc;
 }
 
-template <int U>
-int launch_search(wh_ctx* ctx, hipStream_t st, int B, size_t lds, const WsUtt* d_meta, const int64_t* d_pos, int hop, int tol,
-                  const double* x, int64_t* d_c, int32_t* delta) {
-  if (int rc = wh::allow_lds(wsola_search_kernel<U>, lds)) return rc;
-  return wh::launch(ctx, st, "wsola_search_kernel", wsola_search_kernel<U>, dim3((unsigned)B), dim3(kWsThreads), lds, d_meta,
-                    d_pos, hop, tol, x, d_c, delta);
-}
-
 }  // namespace
 
 extern "C" int wh_wsola(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_off, const int64_t* h_y_off,
@@ -185,13 +125,8 @@ extern "C" int wh_wsola(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x
   int64_t max_out = 0;
   for (int u = 0; u < B; ++u) {
     WsUtt& m = meta[u];
-    m.x_off = h_x_off[u];
-    m.n = h_x_off[u + 1] - h_x_off[u];
-    m.y_off = h_y_off[u];
-    m.n_out = h_y_off[u + 1] - h_y_off[u];
-    m.pos_off = h_pos_off[u];
-    m.n_frames = h_pos_off[u + 1] - h_pos_off[u];
-    if (m.x_off < 0 || m.n < 0 || m.y_off < 0 || m.n_out < 0 || m.pos_off < 0 || m.n_frames < 0)
+    if (!wh::utt_span(h_x_off, u, &m.x_off, &m.n) || !wh::utt_span(h_y_off, u, &m.y_off, &m.n_out) ||
+        !wh::utt_span(h_pos_off, u, &m.pos_off, &m.n_frames))
       return wh::fail_msg(where, "offsets must start at or above 0 and be monotone");
     const int64_t want = m.n_out > 0 ? (m.n_out + hop - 1) / hop + 1 : 0;
     if (m.n_frames != want)
@@ -212,17 +147,14 @@ extern "C" int wh_wsola(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x
   void* d_win = nullptr;
   if (int rc = wh::persistent_upload(ctx, st, "ws.win", h_win, (size_t)(2 * hop - 1) * sizeof(double), &d_win)) return rc;
   // the template and the candidate region, sized from this call's hop and tolerance (5 KB at H = 128, D = 80; 41 KB at the limits)
-  const size_t lds = sizeof(double) * (size_t)(2 * (2 * hop - 1) + 2 * tol);
-  const int per_thread = (2 * tol + 1 + kWsThreads - 1) / kWsThreads;  // candidates a thread runs side by side
-  static_assert(kWsMaxPerThread == 5, "one instantiation per count");
-  int rc = 0;
-  switch (per_thread) {
-    case 1: rc = launch_search<1>(ctx, st, B, lds, d_meta, (const int64_t*)d_pos, hop, tol, x, d_c, delta); break;
-    case 2: rc = launch_search<2>(ctx, st, B, lds, d_meta, (const int64_t*)d_pos, hop, tol, x, d_c, delta); break;
-    case 3: rc = launch_search<3>(ctx, st, B, lds, d_meta, (const int64_t*)d_pos, hop, tol, x, d_c, delta); break;
-    case 4: rc = launch_search<4>(ctx, st, B, lds, d_meta, (const int64_t*)d_pos, hop, tol, x, d_c, delta); break;
-    default: rc = launch_search<5>(ctx, st, B, lds, d_meta, (const int64_t*)d_pos, hop, tol, x, d_c, delta); break;
-  }
+  const size_t lds = sizeof(double) * (size_t)(2 * (2 * hop - 1) + 1 + 2 * tol);  // (+ 1: the pad between the two)
+  // one instantiation per count of candidates that a thread runs side by side
+  const int rc = wh::dispatch_sim_width(tol, [&](auto u) {
+    const auto kernel = wsola_search_kernel<decltype(u)::value>;
+    if (int e = wh::allow_lds(kernel, lds)) return e;
+    return wh::launch(ctx, st, "wsola_search_kernel", kernel, dim3((unsigned)B), dim3(kWsThreads), lds, d_meta, d_pos, hop, tol,
+                      x, d_c, delta);
+  });
   if (rc) return rc;
   WH_LAUNCH(ctx, st, "wsola_ola_kernel", wsola_ola_kernel, dim3((unsigned)((max_out + 255) / 256), B), dim3(256), 0, d_meta, d_c,
             hop, (const double*)d_win, x, y);

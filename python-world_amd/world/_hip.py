@@ -256,6 +256,85 @@ def check(rc):
         raise WorldHipError(load_library().wh_last_error().decode("utf-8", "replace"))
 
 
+# ---- what the stage shims (and the tests that call the C entries directly) share: pointer casts and argument checks ------
+def i64p(a):
+    """The int64_t* of a contiguous int64 NumPy array."""
+    return a.ctypes.data_as(_c_i64p)
+
+
+def i32p(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+
+def f64p(a):
+    return a.ctypes.data_as(ctypes.POINTER(_dbl))
+
+
+def ld(t):
+    """The leading dimension of a 2-D tensor with unit column stride (a single row has no stride to speak of)."""
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def check_rows(rt, name, t, where, min_cols=None):
+    """ValueError unless t is a float64 tensor [frames][columns] with unit column stride — of at least ``min_cols`` columns
+    where that is given (the message then names the shape first, as world.lsf's always did)."""
+    if min_cols is None:
+        if t.dim() != 2 or t.dtype != rt.torch.float64 or t.stride(1) != 1:
+            raise ValueError("%s: %s must be a float64 tensor [frames][columns] with unit column stride, got %s %s strides %s"
+                             % (where, name, t.dtype, tuple(t.shape), tuple(t.stride())))
+        return
+    if t.dim() != 2 or int(t.shape[1]) < min_cols:
+        raise ValueError("%s: %s must be [frames][>= %d], got %s" % (where, name, min_cols, tuple(t.shape)))
+    if t.dtype != rt.torch.float64 or t.stride(1) != 1:
+        raise ValueError("%s: %s must be a float64 tensor with unit column stride, got %s strides %s"
+                         % (where, name, t.dtype, tuple(t.stride())))
+
+
+def check_sample_offsets(x_off, where):
+    """The offsets of the utterances in a flat recording tensor as a contiguous int64 array; ValueError unless they start at
+    or above 0 and do not decrease."""
+    x_off = np.ascontiguousarray(x_off, dtype=np.int64)
+    if x_off.ndim != 1 or len(x_off) < 1 or x_off[0] < 0 or np.any(np.diff(x_off) < 0):
+        raise ValueError("%s: sample offsets must start at or above 0 and not decrease" % where)
+    return x_off
+
+
+def check_output_lengths(y_lengths, where):
+    """One output length per utterance as a list of ints; ValueError for one that is not a non-negative integer."""
+    lens = []
+    for v in y_lengths:
+        if isinstance(v, (bool, np.bool_)) or int(v) != v or int(v) < 0:
+            raise ValueError("%s: an output length must be a non-negative integer, got %r" % (where, v))
+        lens.append(int(v))
+    return lens
+
+
+def check_recording(rt, x_d, x_off, where):
+    """ValueError unless x_d is a flat contiguous float64 tensor that holds every utterance of x_off."""
+    if x_d.dim() != 1 or x_d.dtype != rt.torch.float64 or not x_d.is_contiguous() or int(x_d.shape[0]) < int(x_off[-1]):
+        raise ValueError("%s: x must be a contiguous float64 tensor of at least %d samples" % (where, int(x_off[-1])))
+
+
+def host_recording(x, where):
+    """One recording as a contiguous 1-D float64 host array."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 1:
+        raise ValueError("%s: x must be 1-D, got shape %s" % (where, x.shape))
+    return x
+
+
+@serialised
+def recording_through(where, x, fn):
+    """One host recording through a device function and back, on the default runtime: uploads x, takes the flat tensor
+    y_d = fn(rt, x_d, [0, len(x)]) to the host and raises for the flags the call left (under ``where``)."""
+    x = host_recording(x, where)
+    rt = Runtime.get()
+    with rt.lock, rt.on_stream():
+        out = fn(rt, rt.to_device(x), [0, len(x)]).cpu().numpy()
+    rt.check_flags(where)
+    return out
+
+
 _pool = None
 
 

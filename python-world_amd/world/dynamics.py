@@ -15,8 +15,6 @@ who generates log-f0 over the voiced runs only passes the runs as utterances (fr
 gathered voiced rows); nothing more is built for that here.
 
 The argument checks and the workspace grouping are host code and need neither the library nor a GPU."""
-import ctypes
-
 import numpy as np
 
 from . import _hip
@@ -97,10 +95,6 @@ def check_mlpg_shapes(mean_shape, var_shape, frames, n_win, where="mlpg"):
                      % (where, frames, width, width, tuple(var_shape)))
 
 
-def _win_ptr(win):
-    return win.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-
-
 # ---- device ----------------------------------------------------------------------------------------------------------
 def _check_tensor(rt, name, t, where):
     if t.dtype != rt.torch.float64 or t.stride(-1) != 1:
@@ -120,7 +114,7 @@ def delta_features_device(rt, batch, x, windows=HTS_WINDOWS):
     with rt.lock, rt.on_stream():
         out = rt.empty((batch.total_frames, len(win) * d))
         _hip.check(rt.lib.wh_delta_features(rt.ctx, rt.stream(), batch.handle, rt.ptr(x), int(x.stride(0)) if x.shape[0] > 1 else d,
-                                            d, len(win), half, _win_ptr(win), rt.ptr(out), len(win) * d))
+                                            d, len(win), half, _hip.f64p(win), rt.ptr(out), len(win) * d))
     return out
 
 
@@ -158,7 +152,7 @@ def mlpg_device(rt, batch, mean, var, windows=HTS_WINDOWS, max_workspace_bytes=D
                 continue
             g = batch if (u0, u1) == (0, n_utt) else _sub_batch(rt, batch, u0, u1)
             _hip.check(rt.lib.wh_mlpg(rt.ctx, rt.stream(), g.handle, rt.ptr(mean[f0:f1]), ldm,
-                                      rt.ptr(var[f0:f1] if per_frame else var), ldv, d, n_win, half, _win_ptr(win),
+                                      rt.ptr(var[f0:f1] if per_frame else var), ldv, d, n_win, half, _hip.f64p(win),
                                       rt.ptr(out[f0:f1]), d, rt.ptr(piv[f0:f1]) if want_pivots else None))
     return (out, piv) if want_pivots else out
 

@@ -25,7 +25,6 @@ and a conversion is scored by the log-spectral distortion of two rows' envelopes
 Alignment.lsd_db — which wh_lsf_distortion forms from the two rows in product form, without either envelope in memory.
 
 The tables and the argument checks are host code and need neither the library nor a GPU."""
-import ctypes
 import functools
 
 import numpy as np
@@ -84,40 +83,24 @@ def bin_table(k_bins):
     return c
 
 
-def _dp(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-
-
-def _check_rows(rt, name, t, where, min_cols):
-    if t.dim() != 2 or int(t.shape[1]) < min_cols:
-        raise ValueError("%s: %s must be [frames][>= %d], got %s" % (where, name, min_cols, tuple(t.shape)))
-    if t.dtype != rt.torch.float64 or t.stride(1) != 1:
-        raise ValueError("%s: %s must be a float64 tensor with unit column stride, got %s strides %s"
-                         % (where, name, t.dtype, tuple(t.stride())))
-
-
-def _ld(t):
-    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
-
-
 # ---- device ----------------------------------------------------------------------------------------------------------
 def autocorr_device(rt, spec_d, order):
     """Lags 0 .. order of every row of a power spectrogram [F][K]: [F][order + 1]."""
-    _check_rows(rt, "spec", spec_d, "autocorr", 3)
+    _hip.check_rows(rt, "spec", spec_d, "autocorr", 3)
     f, k_bins = (int(v) for v in spec_d.shape)
     check_order(order, "autocorr", k_bins)
-    return feature_matmul_device(rt, spec_d, f, k_bins, _ld(spec_d), autocorr_table(k_bins, int(order)))
+    return feature_matmul_device(rt, spec_d, f, k_bins, _hip.ld(spec_d), autocorr_table(k_bins, int(order)))
 
 
 def levinson_device(rt, r_d, order, want_reflection=False):
     """wh_lpc_levinson on autocorrelation rows [F][>= order + 1]: (a [F][order + 1], E [F], reflection [F][order] or None)."""
-    _check_rows(rt, "r", r_d, "levinson", int(order) + 1)
+    _hip.check_rows(rt, "r", r_d, "levinson", int(order) + 1)
     if int(order) != order or not 1 <= order <= MAX_ORDER:
         raise ValueError("levinson: the order must be an integer in [1, %d], got %r" % (MAX_ORDER, order))
     f, p = int(r_d.shape[0]), int(order)
     a, e = rt.empty((f, p + 1)), rt.empty((f,))
     k = rt.empty((f, p)) if want_reflection else None
-    _hip.check(rt.lib.wh_lpc_levinson(rt.ctx, rt.stream(), rt.ptr(r_d), f, _ld(r_d), p, rt.ptr(a), p + 1, rt.ptr(e),
+    _hip.check(rt.lib.wh_lpc_levinson(rt.ctx, rt.stream(), rt.ptr(r_d), f, _hip.ld(r_d), p, rt.ptr(a), p + 1, rt.ptr(e),
                                       rt.ptr(k), p))
     return a, e, k
 
@@ -125,22 +108,22 @@ def levinson_device(rt, r_d, order, want_reflection=False):
 def lsf_from_lpc_device(rt, a_d, want_level=False):
     """wh_lsf_from_lpc on predictor rows [F][p + 1]: the cosines of the line spectral frequencies [F][p], descending;
     ``want_level``: (x, level int32 [F]) — the grid level that found every root of the frame, 0 for a flagged one."""
-    _check_rows(rt, "a", a_d, "lsf_from_lpc", 3)
+    _hip.check_rows(rt, "a", a_d, "lsf_from_lpc", 3)
     f, p = int(a_d.shape[0]), check_order(int(a_d.shape[1]) - 1, "lsf_from_lpc")
     x = rt.empty((f, p))
     level = rt.empty((f,), dtype=rt.torch.int32) if want_level else None
     grid = grid_table()
-    _hip.check(rt.lib.wh_lsf_from_lpc(rt.ctx, rt.stream(), rt.ptr(a_d), f, _ld(a_d), p, _dp(grid), len(grid), rt.ptr(x), p,
-                                      rt.ptr(level)))
+    _hip.check(rt.lib.wh_lsf_from_lpc(rt.ctx, rt.stream(), rt.ptr(a_d), f, _hip.ld(a_d), p, _hip.f64p(grid), len(grid),
+                                      rt.ptr(x), p, rt.ptr(level)))
     return (x, level) if want_level else x
 
 
 def envelope_device(rt, ex_d, k_bins):
     """wh_lsf_envelope on rows [E, x_1 .. x_p] (gain and COSINES): the power spectrum [F][k_bins]."""
-    _check_rows(rt, "rows", ex_d, "lsf_envelope", 3)
+    _hip.check_rows(rt, "rows", ex_d, "lsf_envelope", 3)
     f, p = int(ex_d.shape[0]), check_order(int(ex_d.shape[1]) - 1, "lsf_envelope")
     out = rt.empty((f, int(k_bins)))
-    _hip.check(rt.lib.wh_lsf_envelope(rt.ctx, rt.stream(), rt.ptr(ex_d), f, _ld(ex_d), p, _dp(bin_table(int(k_bins))),
+    _hip.check(rt.lib.wh_lsf_envelope(rt.ctx, rt.stream(), rt.ptr(ex_d), f, _hip.ld(ex_d), p, _hip.f64p(bin_table(int(k_bins))),
                                       int(k_bins), rt.ptr(out), int(k_bins)))
     return out
 
@@ -187,7 +170,7 @@ def repair_device(rt, w, min_gap, want_changed=False, out=None):
     """wh_lsf_repair: the angles [F][p] (a column slice of the rows is fine) made decodable, in one pass — repair_rows'
     arithmetic step for step, the same bits.  ``min_gap`` > 0.  ``out``: where to (w itself: in place); a new tensor when
     None.  ``want_changed``: (angles, changed int32 [F]) — how many angles of each frame the repair moved."""
-    _check_rows(rt, "w", w, "repair", 2)
+    _hip.check_rows(rt, "w", w, "repair", 2)
     f, p = int(w.shape[0]), int(w.shape[1])
     if p > MAX_ORDER:
         raise ValueError("repair: rows of %d angles; the kernel takes 2 .. %d" % (p, MAX_ORDER))
@@ -198,12 +181,12 @@ def repair_device(rt, w, min_gap, want_changed=False, out=None):
         if out is None:
             out = rt.empty((f, p))
         else:
-            _check_rows(rt, "out", out, "repair", 2)
+            _hip.check_rows(rt, "out", out, "repair", 2)
             if tuple(out.shape) != (f, p):
                 raise ValueError("repair: out must be %s, got %s" % ((f, p), tuple(out.shape)))
         changed = rt.empty((f,), dtype=rt.torch.int32) if want_changed else None
-        _hip.check(rt.lib.wh_lsf_repair(rt.ctx, rt.stream(), rt.ptr(w), f, _ld(w), p, gap, float(np.pi - gap), rt.ptr(out),
-                                        _ld(out), rt.ptr(changed)))
+        _hip.check(rt.lib.wh_lsf_repair(rt.ctx, rt.stream(), rt.ptr(w), f, _hip.ld(w), p, gap, float(np.pi - gap), rt.ptr(out),
+                                        _hip.ld(out), rt.ptr(changed)))
     return (out, changed) if want_changed else out
 
 
@@ -211,7 +194,7 @@ def ilsf_device(rt, rows_d, fft_size, min_gap=0.0):
     """Rows [F][p + 1] = [log E, w_1 .. w_p] -> the power spectrum [F][fft_size // 2 + 1].  ``min_gap`` = 0: the rows are
     used as they are; > 0: repaired first (module docstring; wh_lsf_repair)."""
     k_bins = check_fft_size(fft_size)
-    _check_rows(rt, "rows", rows_d, "ilsf", 3)
+    _hip.check_rows(rt, "rows", rows_d, "ilsf", 3)
     p = check_order(int(rows_d.shape[1]) - 1, "ilsf")
     gap = check_min_gap(min_gap, p, "ilsf")
     torch = rt.torch
@@ -237,8 +220,8 @@ def distortion_sums_device(rt, ex_a, ex_b, k_bins, idx_a=None, idx_b=None):
     """wh_lsf_distortion on rows [., x_1 .. x_p] (COSINES, as envelope_device takes them): [n_pairs][2] = (sum over the
     bins of t, sum of t * t), t = log(A2_a / A2_b).  Pair n is row idx_a[n] against row idx_b[n] (int64 device tensors,
     batch-global frame indices as Alignment.path_a / path_b hold them), or row n where an index is None."""
-    _check_rows(rt, "rows_a", ex_a, "lsf_distortion", 3)
-    _check_rows(rt, "rows_b", ex_b, "lsf_distortion", 3)
+    _hip.check_rows(rt, "rows_a", ex_a, "lsf_distortion", 3)
+    _hip.check_rows(rt, "rows_b", ex_b, "lsf_distortion", 3)
     p = check_order(int(ex_a.shape[1]) - 1, "lsf_distortion")
     if int(ex_b.shape[1]) != p + 1:
         raise ValueError("lsf_distortion: rows of order %d against rows of order %d" % (p, int(ex_b.shape[1]) - 1))
@@ -248,9 +231,9 @@ def distortion_sums_device(rt, ex_a, ex_b, k_bins, idx_a=None, idx_b=None):
     idx_a, idx_b = _index(rt, idx_a, n_pairs, "idx_a"), _index(rt, idx_b, n_pairs, "idx_b")
     with rt.lock, rt.on_stream():
         out = rt.empty((n_pairs, 2))
-        _hip.check(rt.lib.wh_lsf_distortion(rt.ctx, rt.stream(), rt.ptr(ex_a), int(ex_a.shape[0]), _ld(ex_a), rt.ptr(ex_b),
-                                            int(ex_b.shape[0]), _ld(ex_b), p, rt.ptr(idx_a), rt.ptr(idx_b), n_pairs,
-                                            _dp(bin_table(int(k_bins))), int(k_bins), rt.ptr(out)))
+        _hip.check(rt.lib.wh_lsf_distortion(rt.ctx, rt.stream(), rt.ptr(ex_a), int(ex_a.shape[0]), _hip.ld(ex_a), rt.ptr(ex_b),
+                                            int(ex_b.shape[0]), _hip.ld(ex_b), p, rt.ptr(idx_a), rt.ptr(idx_b), n_pairs,
+                                            _hip.f64p(bin_table(int(k_bins))), int(k_bins), rt.ptr(out)))
     return out
 
 
@@ -273,8 +256,8 @@ def distortion_device(rt, rows_a, rows_b, fft_size, idx_a=None, idx_b=None, gain
     (wh_lsf_distortion).  Pair n is row idx_a[n] of rows_a against row idx_b[n] of rows_b, or row n where an index is
     None.  ``gain=False`` leaves the best constant gain out.  The sign of the cross term: distortion_db."""
     k_bins = check_fft_size(fft_size, "lsf_distortion")
-    _check_rows(rt, "rows_a", rows_a, "lsf_distortion", 3)
-    _check_rows(rt, "rows_b", rows_b, "lsf_distortion", 3)
+    _hip.check_rows(rt, "rows_a", rows_a, "lsf_distortion", 3)
+    _hip.check_rows(rt, "rows_b", rows_b, "lsf_distortion", 3)
     torch = rt.torch
     with rt.lock, rt.on_stream():
         # the kernel takes rows of p + 1 columns and does not read column 0: the cosines go into columns 1 .. p of a

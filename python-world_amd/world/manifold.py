@@ -491,7 +491,7 @@ def dense_stack_device(rt, x_d, stack, seg_off=None, window=0, in_shift=None, ou
         raise ValueError("dense_stack: rows must be contiguous")
     _hip.check(rt.lib.wh_dense_stack(
         rt.ctx, rt.stream(), rt.ptr(x_d), n, d, int(x_d.stride(0)) if n else d,
-        seg.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(seg) - 1, window, ish_p, len(stack),
+        _hip.i64p(seg), len(seg) - 1, window, ish_p, len(stack),
         stack._units.ctypes.data_as(vp), stack._acts.ctypes.data_as(vp), stack._w64.ctypes.data_as(vp),
         stack._b64.ctypes.data_as(vp), c0, n_out, tap_layer, rt.ptr(tap) if tap is not None else vp(None),
         stack.units[tap_layer] if tap_layer >= 0 else 0, int(bool(tap_f32)), osh_p, rt.ptr(out), n_out, stack.tag))

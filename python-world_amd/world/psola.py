@@ -19,7 +19,6 @@ period_track / source_map compute on the host.
 default_params, period_track, source_map, mark_capacity, smark_capacity and check_psola_args are host code and need neither
 the library nor a GPU."""
 import collections
-import ctypes
 
 import numpy as np
 
@@ -116,17 +115,11 @@ def check_psola_args(x_off, y_lengths, p, where="psola"):
     offsets of the recordings, the outputs, the analysis track, the two target tracks, and the mark lists at their
     capacities."""
     check_params(p, where)
-    x_off = np.ascontiguousarray(x_off, dtype=np.int64)
+    x_off = _hip.check_sample_offsets(x_off, where)
     n = len(x_off) - 1
-    if x_off.ndim != 1 or n < 0 or x_off[0] < 0 or np.any(np.diff(x_off) < 0):
-        raise ValueError("%s: sample offsets must start at or above 0 and not decrease" % where)
     if len(y_lengths) != n:
         raise ValueError("%s: %d utterances and %d output lengths" % (where, n, len(y_lengths)))
-    lens = []
-    for v in y_lengths:
-        if isinstance(v, (bool, np.bool_)) or int(v) != v or int(v) < 0:
-            raise ValueError("%s: an output length must be a non-negative integer, got %r" % (where, v))
-        lens.append(int(v))
+    lens = _hip.check_output_lengths(y_lengths, where)
     n_in = [int(v) for v in np.diff(x_off)]
 
     def cum(values):
@@ -137,10 +130,6 @@ def check_psola_args(x_off, y_lengths, p, where="psola"):
 
 
 # ---- device ----------------------------------------------------------------------------------------------------------
-def _i64(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-
-
 def _check_track(rt, t, dtype, count, name, where):
     if t.dim() != 1 or t.dtype != dtype or not t.is_contiguous() or int(t.shape[0]) != count:
         raise ValueError("%s: %s must be a contiguous %s tensor of %d entries" % (where, name, dtype, count))
@@ -154,8 +143,7 @@ def psola_device(rt, x_d, x_off, y_lengths, per_a_d, per_s_d, src_d, params, wan
     where = "psola_device"
     x_off, y_off, pa_off, ps_off, mark_off, smark_off = check_psola_args(x_off, y_lengths, params, where)
     torch, n = rt.torch, len(x_off) - 1
-    if x_d.dim() != 1 or x_d.dtype != torch.float64 or not x_d.is_contiguous() or int(x_d.shape[0]) < int(x_off[-1]):
-        raise ValueError("%s: x must be a contiguous float64 tensor of at least %d samples" % (where, int(x_off[-1])))
+    _hip.check_recording(rt, x_d, x_off, where)
     _check_track(rt, per_a_d, torch.int32, int(pa_off[-1]), "per_a", where)
     _check_track(rt, per_s_d, torch.int32, int(ps_off[-1]), "per_s", where)
     _check_track(rt, src_d, torch.int64, int(ps_off[-1]), "src", where)
@@ -170,9 +158,9 @@ def psola_device(rt, x_d, x_off, y_lengths, per_a_d, per_s_d, src_d, params, wan
                    "n_smarks": z(n, torch.int32)}
         if n:
             opt = [rt.ptr(out[k]) if out else None for k in ("marks", "periods", "n_marks", "smarks", "sel", "flip", "n_smarks")]
-            _hip.check(rt.lib.wh_psola(rt.ctx, rt.stream(), n, _i64(x_off), _i64(y_off), _i64(pa_off), _i64(ps_off), _i64(mark_off),
-                                       _i64(smark_off), *[int(v) for v in params], rt.ptr(x_d), rt.ptr(per_a_d), rt.ptr(per_s_d),
-                                       rt.ptr(src_d), rt.ptr(y_d), *opt))
+            offs = [_hip.i64p(a) for a in (x_off, y_off, pa_off, ps_off, mark_off, smark_off)]
+            _hip.check(rt.lib.wh_psola(rt.ctx, rt.stream(), n, *offs, *[int(v) for v in params], rt.ptr(x_d), rt.ptr(per_a_d),
+                                       rt.ptr(per_s_d), rt.ptr(src_d), rt.ptr(y_d), *opt))
     if want_marks:
         out["mark_off"], out["smark_off"] = mark_off, smark_off
         return y_d, y_off, out
@@ -327,32 +315,15 @@ class _Frames:
         self.temporal_positions, self.f0, self.vuv = rt.to_device(tp), rt.to_device(f0), rt.to_device(vuv)
 
 
-def _one(x, where):
-    x = np.ascontiguousarray(x, dtype=np.float64)
-    if x.ndim != 1:
-        raise ValueError("%s: x must be 1-D, got shape %s" % (where, x.shape))
-    return x
-
-
-@_hip.serialised
 def modify_waveform_numpy(fs, x, dat, pitch=1.0, f0=None, duration=1.0, params=None):
-    x = _one(x, "modify_waveform")
-    rt = _hip.Runtime.get()
-    with rt.lock, rt.on_stream():
+    def run(rt, x_d, x_off):
         enc = _Frames(rt, dat, "modify_waveform")
         target = None if f0 is None else rt.to_device(np.ascontiguousarray(f0, dtype=np.float64))
-        y_d, _ = modify_device(rt, rt.to_device(x), [0, len(x)], fs, enc, pitch, target, duration, params)
-        out = y_d.cpu().numpy()
-    rt.check_flags("modify_waveform")
-    return out
+        return modify_device(rt, x_d, x_off, fs, enc, pitch, target, duration, params)[0]
+
+    return _hip.recording_through("modify_waveform", x, run)
 
 
-@_hip.serialised
 def set_pitch_waveform_numpy(fs, x, dat, time, value, params=None):
-    x = _one(x, "set_pitch_waveform")
-    rt = _hip.Runtime.get()
-    with rt.lock, rt.on_stream():
-        y_d, _ = impose_contour_device(rt, rt.to_device(x), [0, len(x)], fs, _Frames(rt, dat, "set_pitch_waveform"), time, value, params)
-        out = y_d.cpu().numpy()
-    rt.check_flags("set_pitch_waveform")
-    return out
+    return _hip.recording_through("set_pitch_waveform", x, lambda rt, x_d, x_off: impose_contour_device(
+        rt, x_d, x_off, fs, _Frames(rt, dat, "set_pitch_waveform"), time, value, params)[0])

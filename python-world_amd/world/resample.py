@@ -2,7 +2,6 @@
 with it before the analysis: example/prosody.py:16-19), executed by the HIP kernel behind wh_resample_poly
 (include/world_hip.h).  The filter is designed here with scipy's own recipe (firwin, the zero pads of resample_poly);
 the device evaluates upfirdn's loop in scipy's summation order, so the result is scipy's, bit for bit."""
-import ctypes
 import functools
 import math
 
@@ -10,9 +9,6 @@ import numpy as np
 
 from . import _hip
 
-_i32p = ctypes.POINTER(ctypes.c_int32)
-_i64p = ctypes.POINTER(ctypes.c_int64)
-_dblp = ctypes.POINTER(ctypes.c_double)
 MAX_RATE = 4096  # largest reduced up / down the library takes (wh_resample_poly)
 
 
@@ -153,11 +149,9 @@ def resample_device(rt, x_d, in_off, ups, downs, window=('kaiser', 5.0), out=Non
     else:
         y_d = out
     if n_utt and out_off[-1] > 0:
-        _hip.check(rt.lib.wh_resample_poly(rt.ctx, rt.stream(), n_utt, in_off.ctypes.data_as(_i64p),
-                                           out_off.ctypes.data_as(_i64p), up_r.ctypes.data_as(_i32p),
-                                           down_r.ctypes.data_as(_i32p), filt_off.ctypes.data_as(_i64p),
-                                           filt_len.ctypes.data_as(_i64p), pre.ctypes.data_as(_i64p),
-                                           filters.ctypes.data_as(_dblp), len(filters), rt.ptr(x_d), rt.ptr(y_d)))
+        _hip.check(rt.lib.wh_resample_poly(rt.ctx, rt.stream(), n_utt, _hip.i64p(in_off), _hip.i64p(out_off),
+                                           _hip.i32p(up_r), _hip.i32p(down_r), _hip.i64p(filt_off), _hip.i64p(filt_len),
+                                           _hip.i64p(pre), _hip.f64p(filters), len(filters), rt.ptr(x_d), rt.ptr(y_d)))
     return y_d, out_off
 
 

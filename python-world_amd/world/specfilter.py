@@ -13,8 +13,6 @@ envelope cancels in the ratio.  The route keeps the source's f0.
     y, ce2 = world.gmm.convert_waveform(wb, batch, x_d, ce, model)                    # convert_compact + the filter
 
 default_hop, window_map and check_filter_args are host code and need neither the library nor a GPU."""
-import ctypes
-
 import numpy as np
 
 from . import _hip
@@ -93,20 +91,6 @@ def check_filter_args(x_off, frame_off, hops, maps, fft_size, kind, cols_num, co
 
 
 # ---- device ----------------------------------------------------------------------------------------------------------
-def _check_rows(rt, name, t, where):
-    if t.dim() != 2 or t.dtype != rt.torch.float64 or t.stride(1) != 1:
-        raise ValueError("%s: %s must be a float64 tensor [frames][columns] with unit column stride, got %s %s strides %s"
-                         % (where, name, t.dtype, tuple(t.shape), tuple(t.stride())))
-
-
-def _ld(t):
-    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
-
-
-def _i64(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-
-
 def filter_device(rt, x_d, x_off, fs, frame_period, fft_size, num, den=None, kind="spectrum", frame_off=None, hop=None,
                   window_map=None):
     """The waveforms ``x_d`` (flat, utterance u at x_off[u]:x_off[u+1]) filtered window by window: ``y_d`` in x's layout,
@@ -121,9 +105,9 @@ def filter_device(rt, x_d, x_off, fs, frame_period, fft_size, num, den=None, kin
     where = "filter_device"
     x_off = np.ascontiguousarray(x_off, dtype=np.int64)
     n = len(x_off) - 1
-    _check_rows(rt, "num", num, where)
+    _hip.check_rows(rt, "num", num, where)
     if den is not None:
-        _check_rows(rt, "den", den, where)
+        _hip.check_rows(rt, "den", den, where)
         if tuple(den.shape) != tuple(num.shape):
             raise ValueError("%s: a numerator %s against a denominator %s" % (where, tuple(num.shape), tuple(den.shape)))
     if frame_off is None:
@@ -131,8 +115,7 @@ def filter_device(rt, x_d, x_off, fs, frame_period, fft_size, num, den=None, kin
     frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
     if len(frame_off) != n + 1 or (n >= 0 and int(frame_off[-1]) > int(num.shape[0])):
         raise ValueError("%s: frame offsets %s do not fit %d utterances and %d rows" % (where, frame_off, n, int(num.shape[0])))
-    if x_d.dim() != 1 or x_d.dtype != rt.torch.float64 or not x_d.is_contiguous() or int(x_d.shape[0]) < int(x_off[-1]):
-        raise ValueError("%s: x must be a contiguous float64 tensor of at least %d samples" % (where, int(x_off[-1])))
+    _hip.check_recording(rt, x_d, x_off, where)
     if hop is None:
         hop = default_hop(fs, frame_period)
     hops = [hop] * n if np.ndim(hop) == 0 else list(hop)
@@ -151,11 +134,9 @@ def filter_device(rt, x_d, x_off, fs, frame_period, fft_size, num, den=None, kin
         if int(x_d.shape[0]) > int(x_off[-1]) or (n and int(x_off[0]) > 0):
             y_d.zero_()  # (samples outside every utterance)
         _hip.check(rt.lib.wh_spectral_filter(
-            rt.ctx, rt.stream(), n, _i64(x_off), _i64(frame_off), _i64(map_off),
-            h_map.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _i64(h_hop), code, rt.ptr(num), _ld(num), rt.ptr(den),
-            _ld(den) if den is not None else 0, width,
-            ctab.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if ctab is not None else None, int(fft_size), rt.ptr(x_d),
-            rt.ptr(y_d)))
+            rt.ctx, rt.stream(), n, _hip.i64p(x_off), _hip.i64p(frame_off), _hip.i64p(map_off), _hip.i32p(h_map),
+            _hip.i64p(h_hop), code, rt.ptr(num), _hip.ld(num), rt.ptr(den), _hip.ld(den) if den is not None else 0, width,
+            _hip.f64p(ctab) if ctab is not None else None, int(fft_size), rt.ptr(x_d), rt.ptr(y_d)))
     return y_d
 
 
@@ -214,9 +195,7 @@ def differential_device(wb, batch, x_d, source, target, hop=None, window_map=Non
 def filter_waveform_numpy(fs, x, dat_num, dat_den=None):
     """x filtered by dat_num's spectrogram over dat_den's (encode() dicts of the same frame grid; dat_den None: by
     dat_num's alone): a NumPy array like x."""
-    x = np.ascontiguousarray(x, dtype=np.float64)
-    if x.ndim != 1:
-        raise ValueError("filter_waveform: x must be 1-D, got shape %s" % (x.shape,))
+    x = _hip.host_recording(x, "filter_waveform")
     sn = np.asarray(dat_num['spectrogram'], dtype=np.float64)
     sd = None if dat_den is None else np.asarray(dat_den['spectrogram'], dtype=np.float64)
     if sn.ndim != 2 or (sd is not None and sd.shape != sn.shape):

@@ -14,7 +14,6 @@ to the target.
 
 window, n_frames, positions, positions_from_map, default_hop_tol, as_fraction, stretched_length and check_wsola_args are
 host code and need neither the library nor a GPU."""
-import ctypes
 from fractions import Fraction
 
 import numpy as np
@@ -100,17 +99,11 @@ def check_wsola_args(x_off, y_lengths, positions, hop, tol, where="wsola"):
     for name, v, lo, hi in (("hop", hop, 1, MAX_HOP), ("tol", tol, 0, MAX_TOL)):
         if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
             raise ValueError("%s: %s must be an integer in [%d, %d], got %r" % (where, name, lo, hi, v))
-    x_off = np.ascontiguousarray(x_off, dtype=np.int64)
+    x_off = _hip.check_sample_offsets(x_off, where)
     n = len(x_off) - 1
-    if x_off.ndim != 1 or n < 0 or x_off[0] < 0 or np.any(np.diff(x_off) < 0):
-        raise ValueError("%s: sample offsets must start at or above 0 and not decrease" % where)
     if len(y_lengths) != n or len(positions) != n:
         raise ValueError("%s: %d utterances, %d output lengths and %d position lists" % (where, n, len(y_lengths), len(positions)))
-    lens = []
-    for v in y_lengths:
-        if isinstance(v, (bool, np.bool_)) or int(v) != v or int(v) < 0:
-            raise ValueError("%s: an output length must be a non-negative integer, got %r" % (where, v))
-        lens.append(int(v))
+    lens = _hip.check_output_lengths(y_lengths, where)
     plist = []
     for u in range(n):
         p = np.asarray(positions[u])
@@ -127,15 +120,6 @@ def check_wsola_args(x_off, y_lengths, positions, hop, tol, where="wsola"):
 
 
 # ---- device ----------------------------------------------------------------------------------------------------------
-def _i64(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-
-
-def _check_x(rt, x_d, x_off, where):
-    if x_d.dim() != 1 or x_d.dtype != rt.torch.float64 or not x_d.is_contiguous() or int(x_d.shape[0]) < int(x_off[-1]):
-        raise ValueError("%s: x must be a contiguous float64 tensor of at least %d samples" % (where, int(x_off[-1])))
-
-
 def wsola_device(rt, x_d, x_off, y_lengths, positions, hop, tol):
     """wh_wsola on the resident recordings ``x_d`` (flat, utterance u at x_off[u]:x_off[u+1]): utterance u becomes
     y_lengths[u] samples whose frames are taken around positions[u] (n_frames(y_lengths[u], hop) nominal input starts; any
@@ -143,15 +127,15 @@ def wsola_device(rt, x_d, x_off, y_lengths, positions, hop, tol):
     their host offsets, and the int32 shift of every frame in the order of the concatenated position lists."""
     where = "wsola_device"
     x_off, y_off, pos_off, pos = check_wsola_args(x_off, y_lengths, positions, hop, tol, where)
-    _check_x(rt, x_d, x_off, where)
+    _hip.check_recording(rt, x_d, x_off, where)
     n = len(x_off) - 1
     win = np.ascontiguousarray(window(hop), dtype=np.float64)
     with rt.lock, rt.on_stream():
         y_d = rt.empty((int(y_off[-1]),))
         delta_d = rt.torch.zeros((int(pos_off[-1]),), dtype=rt.torch.int32, device=rt.device)
         if n:
-            _hip.check(rt.lib.wh_wsola(rt.ctx, rt.stream(), n, _i64(x_off), _i64(y_off), _i64(pos_off), _i64(pos), int(hop),
-                                       int(tol), win.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), rt.ptr(x_d), rt.ptr(y_d),
+            _hip.check(rt.lib.wh_wsola(rt.ctx, rt.stream(), n, _hip.i64p(x_off), _hip.i64p(y_off), _hip.i64p(pos_off),
+                                       _hip.i64p(pos), int(hop), int(tol), _hip.f64p(win), rt.ptr(x_d), rt.ptr(y_d),
                                        rt.ptr(delta_d)))
     return y_d, y_off, delta_d
 
@@ -196,9 +180,7 @@ def shift_pitch_device(rt, x_d, x_off, fs, ratio, hop=None, tol=None, window=('k
     from .resample import resample_device
 
     where = "shift_pitch_device"
-    x_off = np.ascontiguousarray(x_off, dtype=np.int64)
-    if x_off.ndim != 1 or len(x_off) < 1 or x_off[0] < 0 or np.any(np.diff(x_off) < 0):
-        raise ValueError("%s: sample offsets must start at or above 0 and not decrease" % where)
+    x_off = _hip.check_sample_offsets(x_off, where)
     n = len(x_off) - 1
     fracs = [as_fraction(r) for r in _per_utterance(ratio, n, where)]
     with rt.lock, rt.on_stream():
@@ -236,30 +218,10 @@ def log_f0_ratio(ce_source, ce_target):
 
 
 # ---- NumPy forms (World.stretch_waveform / World.shift_pitch_waveform) -------------------------------------------------
-def _one(x, where):
-    x = np.ascontiguousarray(x, dtype=np.float64)
-    if x.ndim != 1:
-        raise ValueError("%s: x must be 1-D, got shape %s" % (where, x.shape))
-    return x
-
-
-@_hip.serialised
 def stretch_waveform_numpy(fs, x, ratio, hop=None, tol=None):
-    x = _one(x, "stretch_waveform")
-    rt = _hip.Runtime.get()
-    with rt.lock, rt.on_stream():
-        y_d, _ = stretch_device(rt, rt.to_device(x), [0, len(x)], fs, ratio, hop, tol)
-        out = y_d.cpu().numpy()
-    rt.check_flags("stretch_waveform")
-    return out
+    return _hip.recording_through("stretch_waveform", x, lambda rt, x_d, x_off: stretch_device(rt, x_d, x_off, fs, ratio, hop, tol)[0])
 
 
-@_hip.serialised
 def shift_pitch_waveform_numpy(fs, x, ratio, hop=None, tol=None):
-    x = _one(x, "shift_pitch_waveform")
-    rt = _hip.Runtime.get()
-    with rt.lock, rt.on_stream():
-        y_d, _ = shift_pitch_device(rt, rt.to_device(x), [0, len(x)], fs, ratio, hop, tol)
-        out = y_d.cpu().numpy()
-    rt.check_flags("shift_pitch_waveform")
-    return out
+    return _hip.recording_through("shift_pitch_waveform", x,
+                                  lambda rt, x_d, x_off: shift_pitch_device(rt, x_d, x_off, fs, ratio, hop, tol)[0])

@@ -1,5 +1,5 @@
-"""Helper of tests/test_hip_exemplar_bounds.py: runs in a process whose WH_LIB is the bounds build (exemplar_bounds,
-registered by tests/_exemplar_variant.py: the kernels of csrc/wh_exemplar.hip index their global buffers and their LDS
+"""Helper of tests/test_hip_exemplar_bounds.py: runs in a process whose WH_LIB is the bounds build (exemplar_bounds in
+the table of tests/_variants.py: the kernels of csrc/wh_exemplar.hip index their global buffers and their LDS
 through wh::ckp there), or without WH_LIB in one that loads the shipped library.  The case list of
 tests/test_hip_exemplar.py (tests/_exemplar_cases.py).  Per case what differs from the reference, the deferred flags, the
 out-of-range record and a digest of the outputs' bytes."""

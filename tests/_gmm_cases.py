@@ -33,24 +33,20 @@ def exact_shapes():
 
 
 # ---- raw calls: tensors in, row strides taken from the tensors -----------------------------------------------------------
-def _ld(t):
-    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
-
-
 def raw_estep(rt, x, mu, whiten, logc, ll=None, gamma=None, rowll=None, best=None, n=None):
     from world import _hip
     m, d = int(mu.shape[0]), int(mu.shape[1])
     n = int(x.shape[0]) if n is None else n
-    _hip.check(rt.lib.wh_gmm_estep(rt.ctx, rt.stream(), rt.ptr(x), n, _ld(x), d, m, rt.ptr(mu), rt.ptr(whiten), rt.ptr(logc),
-                                   rt.ptr(ll), _ld(ll) if ll is not None else m, rt.ptr(gamma),
-                                   _ld(gamma) if gamma is not None else m, rt.ptr(rowll), rt.ptr(best)))
+    _hip.check(rt.lib.wh_gmm_estep(rt.ctx, rt.stream(), rt.ptr(x), n, _hip.ld(x), d, m, rt.ptr(mu), rt.ptr(whiten), rt.ptr(logc),
+                                   rt.ptr(ll), _hip.ld(ll) if ll is not None else m, rt.ptr(gamma),
+                                   _hip.ld(gamma) if gamma is not None else m, rt.ptr(rowll), rt.ptr(best)))
 
 
 def raw_stats(rt, x, gamma, mu, s0, s1, s2, n=None):
     from world import _hip
     m, d = int(mu.shape[0]), int(mu.shape[1])
     n = int(x.shape[0]) if n is None else n
-    _hip.check(rt.lib.wh_gmm_stats(rt.ctx, rt.stream(), rt.ptr(x), n, _ld(x), d, m, rt.ptr(gamma), _ld(gamma), rt.ptr(mu),
+    _hip.check(rt.lib.wh_gmm_stats(rt.ctx, rt.stream(), rt.ptr(x), n, _hip.ld(x), d, m, rt.ptr(gamma), _hip.ld(gamma), rt.ptr(mu),
                                    rt.ptr(s0), rt.ptr(s1), rt.ptr(s2)))
 
 
@@ -58,8 +54,8 @@ def raw_convert(rt, x, mu_x, a, mu_y, out, best=None, g=None, n=None):
     from world import _hip
     m, dx, dy = int(a.shape[0]), int(a.shape[1]), int(a.shape[2])
     n = int(x.shape[0]) if n is None else n
-    _hip.check(rt.lib.wh_gmm_convert(rt.ctx, rt.stream(), rt.ptr(x), n, _ld(x), dx, dy, m, rt.ptr(mu_x), rt.ptr(a), rt.ptr(mu_y),
-                                     rt.ptr(best), rt.ptr(g), _ld(g) if g is not None else m, rt.ptr(out), _ld(out)))
+    _hip.check(rt.lib.wh_gmm_convert(rt.ctx, rt.stream(), rt.ptr(x), n, _hip.ld(x), dx, dy, m, rt.ptr(mu_x), rt.ptr(a), rt.ptr(mu_y),
+                                     rt.ptr(best), rt.ptr(g), _hip.ld(g) if g is not None else m, rt.ptr(out), _hip.ld(out)))
 
 
 def estep_all(rt, x, mu, whiten, logc):

@@ -4,7 +4,6 @@ to double) that need a given grid level, the degenerate rows, the reference resu
 computed once per process and kept read-only), the three C entries called directly — inputs and outputs inside wider
 tensors whose NaN guard bands must survive — and a bit-for-bit comparison."""
 import collections
-import ctypes
 import functools
 
 import numpy as np
@@ -162,14 +161,6 @@ class _Out:
         return w[:, self.pad:self.pad + self.cols].copy(), bool(np.all(np.isnan(guards)))
 
 
-def _ld(t):
-    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
-
-
-def _dp(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-
-
 def run_levinson(rt, r, p, pad=0):
     """wh_lpc_levinson -> {a, e, refl, guards}."""
     from world import _hip
@@ -178,7 +169,7 @@ def run_levinson(rt, r, p, pad=0):
     f = int(r_d.shape[0])
     a, k = _Out(rt, f, p + 1, pad), _Out(rt, f, p, pad)
     e = rt.torch.full((f,), float("nan"), dtype=rt.torch.float64, device=rt.device)
-    _hip.check(rt.lib.wh_lpc_levinson(rt.ctx, rt.stream(), rt.ptr(r_d), f, _ld(r_d), p, rt.ptr(a.view), a.ld, rt.ptr(e),
+    _hip.check(rt.lib.wh_lpc_levinson(rt.ctx, rt.stream(), rt.ptr(r_d), f, _hip.ld(r_d), p, rt.ptr(a.view), a.ld, rt.ptr(e),
                                       rt.ptr(k.view), k.ld))
     (ah, ga), (kh, gk) = a.host(), k.host()
     return {"a": ah, "e": e.cpu().numpy(), "refl": kh, "guards": ga and gk}
@@ -194,7 +185,7 @@ def run_lsf(rt, a, pad=0):
     x = _Out(rt, f, p, pad)
     level = rt.torch.full((f,), -1, dtype=rt.torch.int32, device=rt.device)
     grid = grid_table()
-    _hip.check(rt.lib.wh_lsf_from_lpc(rt.ctx, rt.stream(), rt.ptr(a_d), f, _ld(a_d), p, _dp(grid), len(grid), rt.ptr(x.view),
+    _hip.check(rt.lib.wh_lsf_from_lpc(rt.ctx, rt.stream(), rt.ptr(a_d), f, _hip.ld(a_d), p, _hip.f64p(grid), len(grid), rt.ptr(x.view),
                                       x.ld, rt.ptr(level)))
     xh, gx = x.host()
     return {"x": xh, "level": level.cpu().numpy(), "guards": gx}
@@ -208,7 +199,7 @@ def run_envelope(rt, ex, k_bins, pad=0):
     ex_d = _wide_in(rt, ex, pad)
     f, p = int(ex_d.shape[0]), int(ex_d.shape[1]) - 1
     out = _Out(rt, f, k_bins, pad)
-    _hip.check(rt.lib.wh_lsf_envelope(rt.ctx, rt.stream(), rt.ptr(ex_d), f, _ld(ex_d), p, _dp(bin_table(k_bins)), k_bins,
+    _hip.check(rt.lib.wh_lsf_envelope(rt.ctx, rt.stream(), rt.ptr(ex_d), f, _hip.ld(ex_d), p, _hip.f64p(bin_table(k_bins)), k_bins,
                                       rt.ptr(out.view), out.ld))
     eh, ge = out.host()
     return {"env": eh, "guards": ge}

@@ -3,7 +3,6 @@ tests: rows of angles of every kind a repair can meet, seeded rows of cosines wi
 reference result of every case (tests/_lsf_chain_reference.py, computed once per process and kept read-only) and the two C
 entries called directly — inputs and outputs inside wider tensors whose NaN guard bands must survive."""
 import collections
-import ctypes
 import functools
 
 import numpy as np
@@ -83,6 +82,8 @@ def all_kinds_case(p):
 
 def run_repair(rt, w, gap, hi, pad=0, in_place=False, want_changed=True):
     """wh_lsf_repair -> {out, changed, guards, rc}; in place: the input's own wide tensor is the output."""
+    from world import _hip
+
     w = np.ascontiguousarray(w, dtype=np.float64)
     f, p = w.shape
     torch = rt.torch
@@ -97,7 +98,7 @@ def run_repair(rt, w, gap, hi, pad=0, in_place=False, want_changed=True):
         out = lc._Out(rt, f, p, pad)
         dst, ldo, wide_d = out.view, out.ld, out.wide
     changed = torch.full((f + 2,), -7, dtype=torch.int32, device=rt.device) if want_changed else None
-    rc = rt.lib.wh_lsf_repair(rt.ctx, rt.stream(), rt.ptr(src), f, lc._ld(src) if not in_place else ldo, p, gap, hi,
+    rc = rt.lib.wh_lsf_repair(rt.ctx, rt.stream(), rt.ptr(src), f, _hip.ld(src) if not in_place else ldo, p, gap, hi,
                               rt.ptr(dst), ldo, rt.ptr(changed[1:]) if want_changed else None)
     host = wide_d.cpu().numpy()
     guards = bool(np.all(np.isnan(np.concatenate([host[:, :pad], host[:, pad + p:]], axis=1))))
@@ -171,6 +172,7 @@ def dist_reference(case):
 
 def run_distortion(rt, rows_a, rows_b, k_bins, idx_a=None, idx_b=None, pad=0):
     """wh_lsf_distortion -> {out [n][2], guards, rc}; the output has a guard pair in front and behind."""
+    from world import _hip
     from world.lsf import bin_table
 
     a_d, b_d = lc._wide_in(rt, rows_a, pad), lc._wide_in(rt, rows_b, pad)
@@ -181,9 +183,9 @@ def run_distortion(rt, rows_a, rows_b, k_bins, idx_a=None, idx_b=None, pad=0):
     n = len(rows_a) if idx_a is None and idx_b is None else len(idx_a if idx_a is not None else idx_b)
     wide = torch.full((n + 2, 2), float("nan"), dtype=torch.float64, device=rt.device)
     wide[0] = wide[-1] = -7.0
-    rc = rt.lib.wh_lsf_distortion(rt.ctx, rt.stream(), rt.ptr(a_d), int(a_d.shape[0]), lc._ld(a_d), rt.ptr(b_d),
-                                  int(b_d.shape[0]), lc._ld(b_d), p, rt.ptr(ia), rt.ptr(ib), n,
-                                  bin_table(k_bins).ctypes.data_as(ctypes.POINTER(ctypes.c_double)), k_bins, rt.ptr(wide[1:]))
+    rc = rt.lib.wh_lsf_distortion(rt.ctx, rt.stream(), rt.ptr(a_d), int(a_d.shape[0]), _hip.ld(a_d), rt.ptr(b_d),
+                                  int(b_d.shape[0]), _hip.ld(b_d), p, rt.ptr(ia), rt.ptr(ib), n,
+                                  _hip.f64p(bin_table(k_bins)), k_bins, rt.ptr(wide[1:]))
     host = wide.cpu().numpy()
     return {"out": host[1:-1].copy(), "guards": bool(np.all(host[0] == -7.0) and np.all(host[-1] == -7.0)), "rc": rc}
 

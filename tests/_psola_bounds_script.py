@@ -1,4 +1,4 @@
-"""Helper of tests/test_hip_psola_bounds.py: runs in a process whose WH_LIB is the bounds build (tests/_psola_variant.py,
+"""Helper of tests/test_hip_psola_bounds.py: runs in a process whose WH_LIB is the bounds build (tests/_variants.py,
 psola_bounds: the three kernels of csrc/wh_psola.hip index their global buffers, the grain records and their LDS through
 wh::ckp there), or without WH_LIB in one that loads the shipped library.  The case list of tests/test_hip_psola.py
 (tests/_psola_cases.py), the hostile tracks included.  Per case what differs from the reference, the deferred flags, the

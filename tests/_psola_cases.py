@@ -17,7 +17,6 @@ A case is one CALL: Params(grid, hop, tol, pmin, smin, norm) and a batch of utte
                 ("wild", None): anywhere from far in front of the utterance to far behind it, in no order;
                 ("far", None): the same with +- 2^62 and the ends of the int64 range among them."""
 import collections
-import ctypes
 import functools
 
 import numpy as np
@@ -204,15 +203,13 @@ def reference(case):
     return tuple(out)
 
 
-def _i64(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-
-
 def call(rt, n_utt, x_off, y_off, pa_off, ps_off, mark_off, smark_off, params, x, per_a, per_s, src, y, marks=None, periods=None,
          n_marks=None, smarks=None, sel=None, flip=None, n_smarks=None):
     """The C entry with host arrays made from lists (pointers pass as they are); returns rc."""
+    from world import _hip
+
     offs = [None if a is None else np.ascontiguousarray(a, dtype=np.int64) for a in (x_off, y_off, pa_off, ps_off, mark_off, smark_off)]
-    return rt.lib.wh_psola(rt.ctx, rt.stream(), n_utt, *(None if a is None else _i64(a) for a in offs), *[int(v) for v in params],
+    return rt.lib.wh_psola(rt.ctx, rt.stream(), n_utt, *(None if a is None else _hip.i64p(a) for a in offs), *[int(v) for v in params],
                            x, per_a, per_s, src, y, marks, periods, n_marks, smarks, sel, flip, n_smarks)
 
 

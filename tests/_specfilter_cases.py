@@ -6,7 +6,6 @@ rows inside wider tensors whose NaN guard bands must survive, the output between
 A case is one CALL: a batch of utterances that share the transform length, the kind and the presence of a denominator;
 hop, length, frame count and row map are per utterance."""
 import collections
-import ctypes
 import functools
 
 import numpy as np
@@ -130,12 +129,9 @@ def _wide(rt, a, pad):
     return rt.to_device(wide)
 
 
-def _i64(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-
-
 def call(rt, n_utt, x_off, frame_off, map_off, h_map, hops, kind, num_d, ldn, den_d, ldd, width, fft_size, x_d, y_d, cos=True):
     """The C entry with host arrays made from lists; returns rc."""
+    from world import _hip
     from world.lsf import bin_table
 
     x_off, frame_off, map_off = (np.ascontiguousarray(a, dtype=np.int64) for a in (x_off, frame_off, map_off))
@@ -143,9 +139,8 @@ def call(rt, n_utt, x_off, frame_off, map_off, h_map, hops, kind, num_d, ldn, de
     hops = np.ascontiguousarray(hops, dtype=np.int64)
     ctab = bin_table(int(fft_size) // 2 + 1) if cos and kind == 1 and fft_size in FFT_SIZES else None
     return rt.lib.wh_spectral_filter(
-        rt.ctx, rt.stream(), n_utt, _i64(x_off), _i64(frame_off), _i64(map_off),
-        h_map.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _i64(hops), kind, num_d, ldn, den_d, ldd, width,
-        ctab.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if ctab is not None else None, fft_size, x_d, y_d)
+        rt.ctx, rt.stream(), n_utt, _hip.i64p(x_off), _hip.i64p(frame_off), _hip.i64p(map_off), _hip.i32p(h_map),
+        _hip.i64p(hops), kind, num_d, ldn, den_d, ldd, width, _hip.f64p(ctab) if ctab is not None else None, fft_size, x_d, y_d)
 
 
 def run(rt, case, only=None, num=None):

@@ -42,6 +42,8 @@ VARIANTS = {
     "lsf_chain_bounds": _checked("wh_lsf_chain"),
     "specfilter_bounds": _checked("wh_specfilter"),
     "wsola_bounds": _checked("wh_wsola"),
+    "exemplar_bounds": _checked("wh_exemplar"),
+    "psola_bounds": _checked("wh_psola"),
     # wh_fft_probe.hip compiled as wh_api.hip is, without contraction (tests/test_hip_fft_engine.py, d)
     "nocontract": {"wh_fft_probe": ["-ffp-contract=off"]},
 }

@@ -13,7 +13,6 @@ utterance.  An utterance is (signal, n, positions, parameter):
                 anywhere from 3 H + D in front of the utterance to as far behind it, in no order; far n_out: the same
                 with the ends of the int64 range and +- 2^62 among them."""
 import collections
-import ctypes
 import functools
 
 import numpy as np
@@ -144,16 +143,14 @@ def reference(case):
     return tuple(out)
 
 
-def _i64(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-
-
 def call(rt, n_utt, x_off, y_off, pos_off, pos, hop, tol, x_d, y_d, delta_d, win=True):
     """The C entry with host arrays made from lists (pointers pass as they are); returns rc."""
+    from world import _hip
+
     x_off, y_off, pos_off, pos = (None if a is None else np.ascontiguousarray(a, dtype=np.int64) for a in (x_off, y_off, pos_off, pos))
     w = np.ascontiguousarray(wref.window(hop if 1 <= hop <= wref.MAX_HOP else 1)) if win else None
-    return rt.lib.wh_wsola(rt.ctx, rt.stream(), n_utt, *(None if a is None else _i64(a) for a in (x_off, y_off, pos_off, pos)), hop, tol,
-                           None if w is None else w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), x_d, y_d, delta_d)
+    return rt.lib.wh_wsola(rt.ctx, rt.stream(), n_utt, *(None if a is None else _hip.i64p(a) for a in (x_off, y_off, pos_off, pos)), hop, tol,
+                           None if w is None else _hip.f64p(w), x_d, y_d, delta_d)
 
 
 Y_GUARD, D_GUARD = -7.0, -77777

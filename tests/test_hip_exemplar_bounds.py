@@ -3,12 +3,11 @@ of its kernels compared with the range it may touch): no out-of-range record, no
 shipped library's bytes."""
 import pytest
 
-import _exemplar_variant
 import _variants as V
 
 pytestmark = pytest.mark.gpu
 
-report = V.report_fixture(_exemplar_variant.NAME, "_exemplar_bounds_script.py", shipped=True)
+report = V.report_fixture("exemplar_bounds", "_exemplar_bounds_script.py", shipped=True)
 
 
 def test_the_variant_is_a_bounds_build(report):

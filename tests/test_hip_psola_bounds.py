@@ -7,11 +7,10 @@ records, and the shipped library's bits."""
 import pytest
 
 import _variants as V
-import _psola_variant
 
 pytestmark = pytest.mark.gpu
 
-reports = V.report_fixture(_psola_variant.NAME, "_psola_bounds_script.py", shipped=True)
+reports = V.report_fixture("psola_bounds", "_psola_bounds_script.py", shipped=True)
 
 
 def test_variant_is_a_bounds_build(reports):

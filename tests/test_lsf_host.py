@@ -220,3 +220,28 @@ def test_shape_checks_of_the_lsf_kind():
     with pytest.raises(ValueError, match="'lsf' must have shape"):
         CompactEncoding.from_dicts([dats[0], dict(dats[2], lsf=dats[2]["lsf"][:, :13])])
     assert h.nbytes() == 8 * 12 * (3 + 25 + 5 + 1)
+
+
+def test_row_checks_keep_both_messages():
+    import types
+
+    import torch
+
+    from world import _hip
+
+    rt = types.SimpleNamespace(torch=torch)
+    t = torch.zeros((4, 6), dtype=torch.float64)
+    _hip.check_rows(rt, "rows", t, "w")
+    _hip.check_rows(rt, "rows", t[:, :5], "w", 5)  # (a column slice keeps the unit column stride)
+    assert _hip.ld(t[:, :5]) == 6 and _hip.ld(t[:1, :5]) == 5
+    with pytest.raises(ValueError, match=r"w: rows must be \[frames\]\[>= 7\], got \(4, 6\)"):
+        _hip.check_rows(rt, "rows", t, "w", 7)
+    with pytest.raises(ValueError, match=r"w: rows must be \[frames\]\[>= 3\], got \(4,\)"):
+        _hip.check_rows(rt, "rows", t[:, 0], "w", 3)
+    for bad in (t.float(), t[:, ::2]):
+        with pytest.raises(ValueError, match=r"w: rows must be a float64 tensor with unit column stride, got torch\.float"):
+            _hip.check_rows(rt, "rows", bad, "w", 3)
+        with pytest.raises(ValueError, match=r"w: rows must be a float64 tensor \[frames\]\[columns\] with unit column stride, got"):
+            _hip.check_rows(rt, "rows", bad, "w")
+    with pytest.raises(ValueError, match=r"\[frames\]\[columns\]"):
+        _hip.check_rows(rt, "rows", t[0], "w")

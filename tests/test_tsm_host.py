@@ -91,7 +91,9 @@ def test_argument_checks():
         "hop 0": dict(hop=0), "hop too large": dict(hop=1025), "hop a float": dict(hop=10.0), "hop a bool": dict(hop=True),
         "tol negative": dict(tol=-1), "tol too large": dict(tol=513),
         "offsets decrease": dict(x_off=[0, 80, 70]), "offsets negative": dict(x_off=[-1, 80, 80]),
+        "no offsets": dict(x_off=[], y_lengths=[], positions=[]), "offsets a table": dict(x_off=[[0, 80, 80]]),
         "lengths of another batch": dict(y_lengths=[100]), "negative length": dict(y_lengths=[100, -1]),
+        "a bool length": dict(y_lengths=[100, False]), "a fractional length": dict(y_lengths=[100.5, 0]),
         "list of another length": dict(positions=[pos[0][:-1], pos[1]]),
         "float positions": dict(positions=[pos[0].astype(np.float64), pos[1]]),
         "lists of another batch": dict(positions=pos[:1]),
@@ -118,3 +120,24 @@ def test_log_f0_ratio_on_host_encodings():
         tsm.log_f0_ratio(a, Enc([0.0, 100.0], [0, 0]))
     with pytest.raises(ValueError):
         tsm.log_f0_ratio(a, object())
+
+
+def test_recording_checks():
+    import types
+
+    import torch
+
+    from world import _hip
+
+    rt = types.SimpleNamespace(torch=torch)
+    x = torch.zeros(80, dtype=torch.float64)
+    _hip.check_recording(rt, x, [0, 30, 80], "w")
+    for name, bad in (("short", x[:79]), ("float32", x.float()), ("strided", torch.zeros(160, dtype=torch.float64)[::2]),
+                      ("2-D", x.reshape(1, 80))):
+        with pytest.raises(ValueError, match="w: x must be a contiguous float64 tensor of at least 80 samples"):
+            _hip.check_recording(rt, bad, [0, 30, 80], "w")
+            pytest.fail(name)
+    h = _hip.host_recording([1, 2, 3], "w")
+    assert h.dtype == np.float64 and h.flags.c_contiguous and h.tolist() == [1.0, 2.0, 3.0]
+    with pytest.raises(ValueError, match=r"w: x must be 1-D, got shape \(2, 3\)"):
+        _hip.host_recording(np.zeros((2, 3)), "w")
