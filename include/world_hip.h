@@ -675,6 +675,28 @@ int wh_spectral_filter(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_
                        int64_t ldn, const double* den, int64_t ldd, int p_or_kbins, const double* h_cos, int fft_size,
                        const double* x, double* y);
 
+/* ---- The same filter with mel-cepstral gain rows, in closed form (no counterpart in the reference's library) ------------- */
+/* ABI 127; tests/_melcep_reference.py is the same contract in NumPy.  Windows, row map, segment,
+ * response, overlap-add, limits and everything under "part of the contract" are wh_spectral_filter's; only the gain
+ * differs.  Rows are mel-cepstra c[0 .. m], m = order, 1 <= m <= 64 (any parity; ldn, ldd >= m + 1), on the axis of a
+ * first-order all-pass warp alpha, -1 < alpha < 1: beta(w) = w + 2 atan2(alpha sin w, 1 - alpha cos w), beta_k =
+ * beta(pi k / (K - 1)).  They code a POWER spectrum as log P[k] = 2 sum_j c[j] cos(j beta_k) (the SPTK convention).
+ *   gain      d[j] = num[r][j] - den[r][j], j <= m, of row r = map[w] (den == NULL: num[r][j]);
+ *             G_w[k] = exp(sum_j d[j] cos(j beta_k)) * cis(-sum_j d[j] sin(j beta_k)), k < K: the transfer function
+ *             exp(sum_j d[j] z~^-j), z~^-1 = (z^-1 - alpha) / (1 - alpha z^-1), on the unit circle.  It is minimum phase
+ *             as it stands: no logarithm, no cepstral fold, and neither envelope is ever in memory.
+ *   tables    h_cos_beta[k] = cos(beta_k), h_sin_beta[k] = sin(beta_k): HOST [K] each, the caller's (world.melcep.warp_tables);
+ *             the library computes no trigonometric table of its own and never sees alpha.
+ * Not part of the contract: how the two sums are evaluated (one Clenshaw recurrence per bin, b_j = d[j] + 2 cos(beta) b_{j+1}
+ * - b_{j+2}; re = d[0] + cos(beta) b_1 - b_2, im = sin(beta) b_1, which may fuse); results are compared at tolerances.
+ * A NaN in row r reaches the samples [s_w, s_w + N) of the windows with map[w] == r and nothing else.  NULL tables, an
+ * order outside [1, 64] and a leading dimension below order + 1 fail before anything is launched, like every other wrong
+ * argument.  wh_spectral_filter itself keeps refusing kind 2. */
+int wh_melcep_filter(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_off, const int64_t* h_frame_off,
+                     const int64_t* h_map_off, const int32_t* h_map, const int64_t* h_hop, const double* num, int64_t ldn,
+                     const double* den, int64_t ldd, int order, const double* h_cos_beta, const double* h_sin_beta,
+                     int fft_size, const double* x, double* y);
+
 /* ---- Waveform-similarity overlap-add: the timing of a recording changed without analysis and synthesis (no counterpart) -- */
 /* ABI 122; tests/_wsola_reference.py is the same contract in NumPy.  Stretching a recording by the f0
  * ratio with this and resampling it back by the inverse ratio (wh_resample_poly) moves its f0 and keeps its duration: the

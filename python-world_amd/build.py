@@ -36,7 +36,7 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 #     response_pair and noise_conv_groups only (wh_resp_pulse.h, wh_resp_pair.h).
 #   * wh_specfilter.hip (the spectral filter of recordings: the Requiem filter's chain on another geometry) is built like
 #     wh_requiem.hip: unfused — the products of its LSF gain are the contract's, rounded one by one — but for
-#     min_phase_response's own pragma.
+#     min_phase_response's own pragma (and, for mel-cepstral rows, exponent_response's and the recurrence's in front of it).
 #   * wh_wsola.hip (waveform-similarity overlap-add) has no entry below and no pragma: its scores are sums of products
 #     rounded one by one, compared bit for bit with tests/_wsola_reference.py.
 #   * wh_psola.hip (pitch-synchronous overlap-add) likewise: the scores and the window's cubic are rounded operation by

@@ -175,7 +175,7 @@ static thread_local int64_t g_bounds_last[4] = {0, 0, 0, 0};
 
 extern "C" {
 
-int wh_version(void) { return 126; }
+int wh_version(void) { return 127; }
 const char* wh_last_error(void) { return g_last_error.c_str(); }
 
 int wh_device_count(int* count) {

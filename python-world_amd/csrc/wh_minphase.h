@@ -158,4 +158,41 @@ __device__ __forceinline__ void min_phase_response(wh::ckp<double2> zb, wh::ckp<
   mp_fft<M, true, GT, FT, WAVE>(zb, tw_base + M);
 }
 
+// The same response from the EXPONENT of a transfer function that is minimum phase as it stands — a mel-cepstrum on a
+// warped axis, H = exp(sum_j d[j] z~^-j) (wh_specfilter.hip, kind 2): no logarithm, no cepstral fold and none of the two
+// forward transforms; only the tail of min_phase_response from its comment "minimum-phase spectrum" on.
+//   `expo(k0, k1)`: (re_0, im_0, re_1, im_1), the exponents re - i im of the bins k0 and k1 = M - k0 (0 <= k <= N/2),
+//   computed by the thread that owns the pair; bin k of the spectrum is exp(re) cis(-im), times mul(k, .).
+//   in: zb is FREE (nobody reads it) and whatever mul reads is visible;  out: time-domain response N * h[n] in zr.
+// (The lines from cis_pair_call to the inverse transform are min_phase_response's own, repeated here so that the chains
+// of response_kernel and req_filter_kernel compile as they did: DESIGN section 23 names the merge as a follow-up.)
+template <int N, int GT, class Expo, class Mul = SpectrumIdentity>
+__device__ __forceinline__ void exponent_response(wh::ckp<double2> zb, wh::ckp<const double2> tw_base, Expo expo, Mul mul = Mul()) {
+#pragma clang fp contract(fast)
+  constexpr int FT = ft_syn(N);
+  constexpr int M = N / 2;
+  const int gt = WH_TID & (GT - 1);
+  const wh::ckp<const double2> WH_RESTRICT w = tw_base + N;
+#pragma unroll 1
+  for (int k = gt; k <= M / 2; k += GT) {
+    const double2 wk = wh::ldg2(w + k);
+    const double4 e = expo(k, M - k);
+    const double4 cis = cis_pair_call(e.x, -e.y * M_1_PI, e.z, -e.w * M_1_PI);
+    double2 A = mul(k, make_double2(cis.x, cis.y)), B = mul(M - k, make_double2(cis.z, cis.w));
+    if (k == 0) {  // DC and Nyquist bins: only their real parts reach a real output
+      A.y = 0.0;
+      B.y = 0.0;
+    }
+    // pre-pass of the inverse real transform (wh::irfft_lds) on the pair
+    const double er = A.x + B.x, ei = A.y - B.y;
+    const double dr = A.x - B.x, di = A.y + B.y;
+    const double orr = fma(dr, wk.x, di * wk.y);
+    const double oi = fma(di, wk.x, -(dr * wk.y));
+    zb[k] = make_double2(er - oi, ei + orr);
+    if (k != 0) zb[M - k] = make_double2(er + oi, orr - ei);
+  }
+  wh::sync<FT>();
+  mp_fft<M, true, GT, FT, false>(zb, tw_base + M);
+}
+
 }  // namespace

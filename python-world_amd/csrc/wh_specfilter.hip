@@ -12,9 +12,12 @@
 //   * the half log-gain h[k] is formed in the chain's buffer straight from one or two rows: two spectrogram rows
 //     (kind 0), or two rows [log E, x_1 .. x_p] of line spectral frequencies in the cosine domain (kind 1) whose
 //     envelopes are evaluated in product form per bin, exactly as lsf_distortion_kernel forms A2 (wh_lsf_chain.hip) —
-//     neither envelope is ever in memory.
+//     neither envelope is ever in memory;
+//   * or (kind 2, the entry wh_melcep_filter) the rows are mel-cepstra on an all-pass warped axis, whose
+//     difference IS the exponent of a minimum-phase spectrum: per bin one Clenshaw recurrence, then exponent_response —
+//     the tail of the chain alone, without h, the logarithms and the fold's two transforms.
 // Built like wh_requiem.hip: build.py's default -ffp-contract=off (the products of kind 1 are rounded one by one, as
-// the contract states them); only min_phase_response fuses, by its own pragma.
+// the contract states them); only min_phase_response, exponent_response and kind 2's recurrence fuse, by their own pragmas.
 // ================================================================================================
 #include "wh_host.h"
 #include "wh_tid.h"  // (the opaque thread index of the spectral units)
@@ -28,7 +31,10 @@
 namespace {
 
 constexpr int kSfMaxOrder = 64;
-constexpr int kSfKindSpectrum = 0, kSfKindLsf = 1;
+constexpr int kSfKindSpectrum = 0, kSfKindLsf = 1, kSfKindMelcep = 2;
+// kind 2: the window's row difference d[0 .. order] has LDS of its own (order + 1 <= 65 doubles, padded to 16 bytes):
+// the segment's buffer is being read by the product while the bins run their recurrences over d
+constexpr int kSfDiffSlots = 66;
 
 struct SfUtt {
   int64_t x_off;    // first sample of the utterance in x and y
@@ -57,6 +63,11 @@ inline int sf_runf_of(int n, int64_t hop) { return sf_runf(n) > 1 && (sf_runf(n)
 // utterances of the other form), so an utterance's sums are the same alone and inside any batch.  RUNF = 1 (long
 // transforms, long hops): the row is the window's own response, written straight from the transform buffer.
 // Kind lsf stages the doubled roots in the segment's buffer, which is free until h is built: no LDS of their own.
+// Kind 2 (wh_melcep_filter): the rows are mel-cepstra c[0 .. p] on the all-pass warped axis whose cosines and sines the
+// table holds (cos_[k] = cos beta_k, cos_[K + k] = sin beta_k).  exp(sum_j d[j] z~^-j) is minimum phase as it stands, so
+// the thread that owns the pair of bins (k, N/2 - k) evaluates both exponents itself — one Clenshaw recurrence each over
+// d = num - den, read from LDS at one address by every lane (a broadcast) — and goes straight to exponent_response:
+// no logarithm, no h in LDS, and the chain's first two transforms with their barriers are absent.
 template <int N, int RUNF, int KIND>
 __global__ __launch_bounds__(ft_syn(N), 1) void specfilter_kernel(const SfUtt* __restrict__ meta, const int32_t* __restrict__ map_,
                                                                   long long n_map, const double* __restrict__ num_, long long ldn,
@@ -78,7 +89,9 @@ __global__ __launch_bounds__(ft_syn(N), 1) void specfilter_kernel(const SfUtt* _
   const wh::ckp<double> xa = wh::ck_make(reinterpret_cast<double*>(smem) + (N + 2), kSfMaxOrder, wh::WH_CK_LDS_SCRATCH);
   const wh::ckp<double> xb = wh::ck_make(reinterpret_cast<double*>(smem) + (N + 2) + kSfMaxOrder, kSfMaxOrder, wh::WH_CK_LDS_SCRATCH);
   // RUNF > 1: the run's sums, (RUNF - 1) hop + N doubles
-  const wh::ckp<double> acc = wh::ck_make(reinterpret_cast<double*>(smem) + 2 * (N + 2),
+  constexpr int DL = KIND == kSfKindMelcep ? kSfDiffSlots : 0;  // kind 2: d[0 .. p] between the segment and the sums
+  const wh::ckp<double> dl = wh::ck_make(reinterpret_cast<double*>(smem) + 2 * (N + 2), DL, wh::WH_CK_LDS_SCRATCH);
+  const wh::ckp<double> acc = wh::ck_make(reinterpret_cast<double*>(smem) + 2 * (N + 2) + DL,
                                           RUNF > 1 ? (RUNF - 1) * m.hop + N : 0, wh::WH_CK_LDS_OTHER);
   if (m.runf != RUNF || (int64_t)blockIdx.x >= m.n_runs) return;  // (uniform over the workgroup)
   const int64_t hop = m.hop;
@@ -94,10 +107,10 @@ __global__ __launch_bounds__(ft_syn(N), 1) void specfilter_kernel(const SfUtt* _
   }
   const wh::ckp<const double> xu = wh::ck_make(x_ + m.x_off, m.ny, wh::WH_CK_WAVEFORM);
   const wh::ckp<const int32_t> map = wh::ck_make(map_, n_map, wh::WH_CK_IN);
-  const long long cols = KIND == kSfKindLsf ? p + 1 : K;
+  const long long cols = KIND == kSfKindSpectrum ? K : p + 1;
   const wh::ckp<const double> num = wh::ck_make(num_, (n_rows - 1) * ldn + cols, wh::WH_CK_IN);
   const wh::ckp<const double> den = wh::ck_make(den_, den_ ? (n_rows - 1) * ldd + cols : 0, wh::WH_CK_IN);
-  const wh::ckp<const double> ctab = wh::ck_make(cos_, KIND == kSfKindLsf ? K : 0, wh::WH_CK_TABLE);
+  const wh::ckp<const double> ctab = wh::ck_make(cos_, KIND == kSfKindLsf ? K : KIND == kSfKindMelcep ? 2 * K : 0, wh::WH_CK_TABLE);
 #pragma unroll 1
   for (int64_t w = w0; w <= w1; ++w) {
     const int64_t s = (w - 1) * hop;                       // 0-based sample of the window's first tap
@@ -152,7 +165,12 @@ __global__ __launch_bounds__(ft_syn(N), 1) void specfilter_kernel(const SfUtt* _
       }
       sr[j] = v;
     }
-    if (KIND != kSfKindLsf) {
+    if (KIND == kSfKindMelcep) {
+      // (free: the last window's bins read it in front of their inverse transform's barriers)
+      const int j = WH_TID;
+      if (j <= p) dl[j] = den_ ? num[r * ldn + j] - den[r * ldd + j] : num[r * ldn + j];
+    }
+    if (KIND == kSfKindSpectrum) {
       const wh::ckp<const double> nr = num + r * ldn;
       const wh::ckp<const double> dr = den_ ? den + r * ldd : den;  // (no arithmetic on a null pointer)
       for (int k = WH_TID; k < K; k += FT) {  // Hermitian-mirrored: the input of the chain's first transform
@@ -169,8 +187,35 @@ __global__ __launch_bounds__(ft_syn(N), 1) void specfilter_kernel(const SfUtt* _
     }
     wh::sync<FT>();
     wh::rfft_frame_lds<N, FT>(sb, tw_base);  // (rfft_lds at the Requiem filter's shapes: wh_fft.h)
-    // minimum-phase spectrum of h x segment spectrum (both Hermitian, so is the product), straight into the inverse transform
-    min_phase_response<N, FT>(zb, tw_base, wh::ckp<const double>(), 0.0, [&](int k, double2 e) { return wh::cmul(e, sb[k]); });
+    if constexpr (KIND == kSfKindMelcep) {
+      // exp(sum_j d[j] cos(j beta) - i sum_j d[j] sin(j beta)) x segment spectrum: Clenshaw, b_j = d[j] + 2 cos(beta) b_{j+1}
+      // - b_{j+2}, j = p .. 1; the sums are d[0] + cos(beta) b_1 - b_2 and sin(beta) b_1.  Two bins side by side: their
+      // chains are independent, and one read of d[j] serves both.  (zb is free: the last window's taps were read in front
+      // of a barrier — the run form's own, or this window's transform's.)
+      exponent_response<N, FT>(
+          zb, tw_base,
+          [&](int k0, int k1) {
+#pragma clang fp contract(fast)
+            const double c0 = ctab[k0], c1 = ctab[k1];
+            const double t0 = 2.0 * c0, t1 = 2.0 * c1;
+            double u1 = 0.0, u2 = 0.0, v1 = 0.0, v2 = 0.0;  // b_{j+1}, b_{j+2} of either bin
+#pragma unroll 4
+            for (int j = p; j >= 1; --j) {
+              const double dj = dl[j];
+              const double u0 = dj + t0 * u1 - u2, v0 = dj + t1 * v1 - v2;
+              u2 = u1;
+              u1 = u0;
+              v2 = v1;
+              v1 = v0;
+            }
+            const double d0 = dl[0];
+            return make_double4(d0 + c0 * u1 - u2, ctab[K + k0] * u1, d0 + c1 * v1 - v2, ctab[K + k1] * v1);
+          },
+          [&](int k, double2 e) { return wh::cmul(e, sb[k]); });
+    } else {
+      // minimum-phase spectrum of h x segment spectrum (both Hermitian, so is the product), straight into the inverse transform
+      min_phase_response<N, FT>(zb, tw_base, wh::ckp<const double>(), 0.0, [&](int k, double2 e) { return wh::cmul(e, sb[k]); });
+    }
     const int shift = (int)(s - a_r);  // (w - w0) * hop: where this window's tap 0 falls in the run
     for (int mm = WH_TID; mm < N; mm += FT) {
       const int64_t t = s + mm;
@@ -213,7 +258,8 @@ int launch_specfilter(wh_ctx* ctx, hipStream_t st, int B, const int64_t* max_run
                       const double* den, int64_t ldd, int p, int64_t n_rows, const double* d_cos, const double* x,
                       double* rows, int64_t rows_tot, double* y) {
   constexpr int RUNF = sf_runf(N);
-  const size_t lds = sizeof(double) * 2 * (N + 2) + 64;  // the chain's buffer and the segment's
+  // the chain's buffer and the segment's (+ kind 2's row difference)
+  const size_t lds = sizeof(double) * (2 * (N + 2) + (KIND == kSfKindMelcep ? kSfDiffSlots : 0)) + 64;
   if constexpr (RUNF > 1) {
     if (max_runs[0] > 0) {
       const size_t lds_k = lds + sizeof(double) * (size_t)((RUNF - 1) * max_hop[0] + N);  // + the run's sums
@@ -233,18 +279,14 @@ int launch_specfilter(wh_ctx* ctx, hipStream_t st, int B, const int64_t* max_run
   return 0;
 }
 
-}  // namespace
-
-extern "C" int wh_spectral_filter(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_off, const int64_t* h_frame_off,
-                                  const int64_t* h_map_off, const int32_t* h_map, const int64_t* h_hop, int kind,
-                                  const double* num, int64_t ldn, const double* den, int64_t ldd, int p_or_kbins,
-                                  const double* h_cos, int fft_size, const double* x, double* y) {
-  const char* where = "wh_spectral_filter";
-  if (!ctx) return wh::fail_msg(where, "null argument");
-  WH_ENTER(ctx);
+// Both entries: `where` names the caller in the messages; `kind` has been admitted by it.  Kind 2 takes two HOST tables
+// of K entries (h_cos, h_sin: the warped axis), kind 1 one, kind 0 none.
+int spectral_filter(const char* where, wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_off, const int64_t* h_frame_off,
+                    const int64_t* h_map_off, const int32_t* h_map, const int64_t* h_hop, int kind, const double* num,
+                    int64_t ldn, const double* den, int64_t ldd, int p_or_kbins, const double* h_cos, const double* h_sin,
+                    int fft_size, const double* x, double* y) {
   if (n_utt < 0) return wh::fail_msg(where, "negative utterance count");
   if (n_utt > 65535) return wh::fail_msg(where, "at most 65535 utterances per call");
-  if (kind != kSfKindSpectrum && kind != kSfKindLsf) return wh::fail_msg(where, "kind must be 0 (spectrum) or 1 (lsf)");
   if (!wh::dispatch_fft_size(fft_size, [](auto) {}))
     return wh::fail_msg(where, "fft_size must be a power of two in [512, 4096]");
   const int K = fft_size / 2 + 1;
@@ -253,10 +295,14 @@ extern "C" int wh_spectral_filter(wh_ctx* ctx, void* stream, int n_utt, const in
     p = p_or_kbins;
     if (p < 2 || p > kSfMaxOrder || (p & 1)) return wh::fail_msg(where, "the order p must be even and in [2, 64]");
     if (!h_cos) return wh::fail_msg(where, "null argument");
+  } else if (kind == kSfKindMelcep) {
+    p = p_or_kbins;
+    if (p < 1 || p > kSfMaxOrder) return wh::fail_msg(where, "the order must be in [1, 64]");
+    if (!h_cos || !h_sin) return wh::fail_msg(where, "null table of the warped axis");
   } else if (p_or_kbins != K) {
     return wh::fail_msg(where, "kind spectrum: the rows must have fft_size / 2 + 1 bins");
   }
-  const int64_t cols = kind == kSfKindLsf ? p + 1 : K;
+  const int64_t cols = kind == kSfKindSpectrum ? K : p + 1;
   if (ldn < cols) return wh::fail_msg(where, "ldn is smaller than a row");
   if (den && ldd < cols) return wh::fail_msg(where, "ldd is smaller than a row");
   if (n_utt == 0) return 0;
@@ -307,14 +353,47 @@ extern "C" int wh_spectral_filter(wh_ctx* ctx, void* stream, int n_utt, const in
   void* d_cos = nullptr;
   if (kind == kSfKindLsf)
     if (int rc = wh::persistent_upload(ctx, st, "sf.bins", h_cos, (size_t)K * sizeof(double), &d_cos)) return rc;
+  if (kind == kSfKindMelcep) {  // [cos beta_k | sin beta_k], one upload
+    std::vector<double> warp(h_cos, h_cos + K);
+    warp.insert(warp.end(), h_sin, h_sin + K);
+    if (int rc = wh::persistent_upload(ctx, st, "sf.warp", warp.data(), warp.size() * sizeof(double), &d_cos)) return rc;
+  }
   int rc = 0;
   wh::dispatch_fft_size(fft_size, [&](auto n) {
     constexpr int N = decltype(n)::value;
-    rc = kind == kSfKindLsf
-             ? launch_specfilter<N, kSfKindLsf>(ctx, st, B, max_runs, max_ny, max_hop, d_meta, (const int32_t*)d_map, n_map,
-                                                num, ldn, den, ldd, p, n_rows, (const double*)d_cos, x, d_rows, rows_tot, y)
-             : launch_specfilter<N, kSfKindSpectrum>(ctx, st, B, max_runs, max_ny, max_hop, d_meta, (const int32_t*)d_map,
-                                                     n_map, num, ldn, den, ldd, p, n_rows, nullptr, x, d_rows, rows_tot, y);
+    auto go = [&](auto k) {
+      return launch_specfilter<N, decltype(k)::value>(ctx, st, B, max_runs, max_ny, max_hop, d_meta, (const int32_t*)d_map, n_map,
+                                                      num, ldn, den, ldd, p, n_rows, (const double*)d_cos, x, d_rows, rows_tot, y);
+    };
+    rc = kind == kSfKindLsf      ? go(std::integral_constant<int, kSfKindLsf>())
+         : kind == kSfKindMelcep ? go(std::integral_constant<int, kSfKindMelcep>())
+                                 : go(std::integral_constant<int, kSfKindSpectrum>());
   });
   return rc;
+}
+
+}  // namespace
+
+extern "C" int wh_spectral_filter(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_off, const int64_t* h_frame_off,
+                                  const int64_t* h_map_off, const int32_t* h_map, const int64_t* h_hop, int kind,
+                                  const double* num, int64_t ldn, const double* den, int64_t ldd, int p_or_kbins,
+                                  const double* h_cos, int fft_size, const double* x, double* y) {
+  const char* where = "wh_spectral_filter";
+  if (!ctx) return wh::fail_msg(where, "null argument");
+  WH_ENTER(ctx);
+  // (mel-cepstral rows have an entry of their own, wh_melcep_filter: they need a second table)
+  if (kind != kSfKindSpectrum && kind != kSfKindLsf) return wh::fail_msg(where, "kind must be 0 (spectrum) or 1 (lsf)");
+  return spectral_filter(where, ctx, stream, n_utt, h_x_off, h_frame_off, h_map_off, h_map, h_hop, kind, num, ldn, den, ldd,
+                         p_or_kbins, h_cos, nullptr, fft_size, x, y);
+}
+
+extern "C" int wh_melcep_filter(wh_ctx* ctx, void* stream, int n_utt, const int64_t* h_x_off, const int64_t* h_frame_off,
+                                const int64_t* h_map_off, const int32_t* h_map, const int64_t* h_hop, const double* num,
+                                int64_t ldn, const double* den, int64_t ldd, int order, const double* h_cos_beta,
+                                const double* h_sin_beta, int fft_size, const double* x, double* y) {
+  const char* where = "wh_melcep_filter";
+  if (!ctx) return wh::fail_msg(where, "null argument");
+  WH_ENTER(ctx);
+  return spectral_filter(where, ctx, stream, n_utt, h_x_off, h_frame_off, h_map_off, h_map, h_hop, kSfKindMelcep, num, ldn, den,
+                         ldd, order, h_cos_beta, h_sin_beta, fft_size, x, y);
 }

@@ -121,6 +121,9 @@ SIGNATURES = {
                                  _vp, _vp, ctypes.c_int64, ctypes.POINTER(_dbl), _int, _vp]),
     "wh_spectral_filter": (_int, [_vp, _vp, _int, _c_i64p, _c_i64p, _c_i64p, ctypes.POINTER(ctypes.c_int32), _c_i64p, _int,
                                   _vp, ctypes.c_int64, _vp, ctypes.c_int64, _int, ctypes.POINTER(_dbl), _int, _vp, _vp]),
+    "wh_melcep_filter": (_int, [_vp, _vp, _int, _c_i64p, _c_i64p, _c_i64p, ctypes.POINTER(ctypes.c_int32), _c_i64p, _vp,
+                                ctypes.c_int64, _vp, ctypes.c_int64, _int, ctypes.POINTER(_dbl), ctypes.POINTER(_dbl), _int,
+                                _vp, _vp]),
     "wh_wsola": (_int, [_vp, _vp, _int, _c_i64p, _c_i64p, _c_i64p, _c_i64p, _int, _int, ctypes.POINTER(_dbl), _vp, _vp, _vp]),
     "wh_psola": (_int, [_vp, _vp, _int, _c_i64p, _c_i64p, _c_i64p, _c_i64p, _c_i64p, _c_i64p, _int, _int, _int, _int, _int, _int,
                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

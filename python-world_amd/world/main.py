@@ -721,6 +721,31 @@ class World(object):
     def get_context(self, X, w=5):
         return _feat.get_context(X, w)
 
+    # ---- mel-cepstra with an all-pass warp, the SPTK convention (world/melcep.py; no counterpart in the reference) ---
+    def encode_melcep(self, spec, order=24, alpha=None, fs=16000):
+        """(N, D) POWER spectrogram (encode()'s 'spectrogram', transposed) -> (N, order + 1) mel-cepstra c[0 .. order] on
+        the all-pass warped axis: log P = 2 sum_j c[j] cos(j beta).  ``alpha`` None: the customary one of ``fs``
+        (world.melcep.DEFAULT_ALPHA: 0.42 at 16 kHz, 0.554 at 48 kHz).  Valid at every sampling rate."""
+        from . import melcep as _mc
+        return _mc.encode_melcep(spec, order, alpha, fs)
+
+    def decode_melcep(self, mc, fft_size, alpha=None, fs=16000):
+        """(N, m + 1) rows of encode_melcep -> the (N, fft_size / 2 + 1) POWER spectrogram they code."""
+        from . import melcep as _mc
+        return _mc.decode_melcep(mc, fft_size, alpha, fs)
+
+    def melcep_distortion(self, mc_a, mc_b):
+        """(N, m + 1) rows against (N, m + 1) rows -> (N,) mel-cepstral distortion in dB,
+        (10 / ln 10) sqrt(2 sum_{j >= 1} (a[j] - b[j])^2): the published MCD."""
+        from . import melcep as _mc
+        return _mc.melcep_distortion(mc_a, mc_b)
+
+    def filter_waveform_melcep(self, fs, x, mc_num, mc_den=None, alpha=None, frame_period=5.0, fft_size=None):
+        """The recording ``x`` filtered frame by frame by the envelope of mc_num over that of mc_den (rows of
+        encode_melcep on x's frame grid; mc_den None: by mc_num's alone), in closed form: neither envelope is formed."""
+        from . import melcep as _mc
+        return _mc.filter_waveform_melcep(fs, x, mc_num, mc_den, alpha, frame_period, fft_size)
+
     # ---- line spectral frequencies (world/lsf.py; no counterpart in the reference's library) -----------------------
     def encode_lsf(self, spec, order=24):
         """(N, D) power spectrogram (encode()'s 'spectrogram', transposed) -> (N, order + 1) rows [log E, w_1 .. w_p]:
